@@ -1,23 +1,26 @@
 #!/usr/bin/env python
 """I2P frames/s of the CoFiI2P forward hot path on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 One process per GPU (torchrun for N > 1; frames shard across ranks, no data-path collective:
 "scaling": "weak").  A step = ONE submission of KITTI-shaped synthetic frames (160x512 image, 20 480 points, KNN-128
 pyramid already resident in HBM) through `CoFiI2P.forward(mode='test')` + the caller-side fine matching
 (evaluation/eval_all.py:99-105) in the fp32-grade arithmetic the reference-named class ships ("bf16x6").  Default: stack-mode
-batches of 16 frames (BASELINE.json configs[2]), 4 submissions in flight; `--batch 1` = one frame per submission (configs[1],
-also measured by every default run and reported as `batch1_pipeline` / `config.batch1_frames_per_s`).
-Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` (dominant kernel,
-timed live with HIP events on the launch stream) and `cpu_baseline` (the CPU oracle = a port of the
-reference's forward, timed on a bounded sample on the host cores).
+batches of 16 frames (BASELINE.json configs[2]), 4 submissions in flight; `--batch 1` = one frame per submission (configs[1]).
+A plain run sets up, warms up, times exactly K steps in one region, writes the outputs of the last timed step when
+`--dump-outputs DIR` is given, and prints ONE JSON line on rank 0 (`value`, `ms_per_step`, ...).
+`--full` adds everything else on record next to `value`: the median over repeated regions, the batch-1 pipeline
+(`batch1_pipeline` / `config.batch1_frames_per_s`), the other arithmetics, `roofline` (dominant kernel, timed live with HIP events on
+the launch stream), the pyramid / loader / stress / training legs and `cpu_baseline` (the CPU oracle = a port of the reference's
+forward, timed on a bounded sample on the host cores); the `--no-*` switches trim that set.
 """
 import argparse
 import json
 import os
 import sys
 import time
+import zlib
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
@@ -625,6 +628,7 @@ class Pipeline:
         self.streams = make_streams(dev, S)
         self.NSLOT = S * max(1, slots_per_stream)   # submission i: stream i % S, hipGraph slot i % NSLOT
         self.pending = [None] * self.NSLOT
+        self.last = None   # [(8-tuple, fine_xy)] of the last submission of the last run()
 
     def run(self, nsteps, base=0):
         nm, model = 0, self.model
@@ -638,7 +642,9 @@ class Pipeline:
         for k in range(self.NSLOT):   # collect in submission order
             sl = (nsteps + k) % self.NSLOT
             if self.pending[sl] is not None:
-                nm = model.finish(self.pending[sl])[4].shape[0]
+                res = model.finish(self.pending[sl])
+                nm = res[4].shape[0]
+                self.last = [(res, self.pending[sl]["fine_xy"][0])]
                 self.pending[sl] = None
         return nm
 
@@ -672,6 +678,7 @@ class BatchPipeline:
             self.batches.append(CoFiI2P.stack_frames([g[0] for g in grp], [g[1] for g in grp]))
         self.streams = make_streams(dev, S)
         self.pending = [None] * S
+        self.last = None   # [(8-tuple, fine_xy)] per frame of the last submission of the last run()
 
     def run(self, nsteps, base=0):
         nm, model = 0, self.model
@@ -684,7 +691,10 @@ class BatchPipeline:
                 self.pending[sl] = model.forward_async(self.slot_base + sl, pyr, img, inputs_stable=not self.copy_inputs)
         for sl in range(self.S):
             if self.pending[sl] is not None:
-                nm = model.finish(self.pending[sl])[0][4].shape[0]
+                res = model.finish(self.pending[sl])
+                nm = res[0][4].shape[0]
+                if sl == (nsteps - 1) % self.S:   # the last submission (its slot is not reused inside the loop)
+                    self.last = list(zip(res, self.pending[sl]["fine_xy"]))
                 self.pending[sl] = None
         return nm
 
@@ -849,6 +859,31 @@ class optional_leg:
         return False
 
 
+OUTPUT_NAMES = ("img_desc", "pc_desc", "img_score", "pc_score", "patches", "fine_pc", "coarse_xy", "coarse_pts", "fine_xy")
+DUMP_BUDGET_BYTES = 60 * 10 ** 6   # payload cap of --dump-outputs (the .npy headers come on top)
+
+
+def dump_outputs(directory, last):
+    """--dump-outputs: what the caller of the timed path received from its last step - per frame of the submission the reference's
+    8-tuple (coarse_xy already x4, as forward returns it) and the fine matches - as <directory>/frame<f>_<name>.npy, floating outputs in
+    float32, integer ones in float64 (exact).  When the step's outputs exceed DUMP_BUDGET_BYTES, every array keeps the same share of its
+    elements, a sample seeded by its name: equal shapes give equal positions, so two builds compare element for element."""
+    arrays = {}
+    for f, (res, fine_xy) in enumerate(last):
+        for name, t in zip(OUTPUT_NAMES, tuple(res) + (fine_xy,)):
+            a = t.detach().cpu().numpy()
+            arrays["frame%02d_%s" % (f, name)] = a.astype(np.float32 if np.issubdtype(a.dtype, np.floating) else np.float64)
+    total = sum(a.nbytes for a in arrays.values())
+    os.makedirs(directory, exist_ok=True)
+    for name, a in arrays.items():
+        keep = a.size if total <= DUMP_BUDGET_BYTES else int(a.size * DUMP_BUDGET_BYTES / total)
+        if keep < a.size:
+            a = a.reshape(-1)[np.sort(np.random.default_rng(zlib.crc32(name.encode())).choice(a.size, keep, replace=False))]
+        np.save(os.path.join(directory, name + ".npy"), a)
+    print("dump-outputs: %d arrays of the last step in %s%s" % (len(arrays), directory, " (seeded sample)" if total > DUMP_BUDGET_BYTES else ""),
+          file=sys.stderr)
+
+
 def timed_repeats(run_steps, barrier, steps, repeats):
     """`repeats` timed regions of EXACTLY `steps` steps each, every one bracketed by barrier + synchronize on both sides -> seconds per region"""
     out = []
@@ -879,7 +914,11 @@ def main():
     ap.add_argument("--no-batch-sweep", action="store_true", help="skip the extra stack-mode batch-4/16 measurements")
     ap.add_argument("--batch", type=int, default=16, help="frames per submission (stack mode; BASELINE configs[2] = 16, configs[1] = 1); a step is one submission")
     ap.add_argument("--stress", action="store_true", help="bench BASELINE configs[4] instead: 896x1600 image, 40960 points (implies --points 40960)")
-    ap.add_argument("--repeats", type=int, default=0, help="timed regions of --steps steps each; the median is reported (0 = 5 when --steps < 100, else 1)")
+    ap.add_argument("--repeats", type=int, default=0, help="timed regions of --steps steps each; the median is reported (0 = 1; with --full 5 when "
+                    "--steps < 100, else 1)")
+    ap.add_argument("--full", action="store_true", help="also run everything on record next to `value` (batch-1 pipeline, other arithmetics, "
+                    "rooflines, pyramid / loader / stress / training legs, CPU baseline; the --no-* switches trim it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the outputs of the last timed step (rank 0) to DIR/<name>.npy")
     ap.add_argument("--distinct-frames", type=int, default=16, help="distinct synthetic frames per rank cycled by the timed loop (16 x 27 MB of "
                     "tables do not fit the 256 MB Infinity Cache)")
     ap.add_argument("--no-f32", action="store_true", help="skip the extra measurements in the other arithmetics (other_arithmetics)")
@@ -954,8 +993,9 @@ def main():
     nmatch = 0
     S = max(1, args.inflight) if not args.eager else 1
     Bsz = max(1, args.batch)
-    repeats = args.repeats if args.repeats > 0 else (5 if args.steps < 100 else 1)
+    repeats = args.repeats if args.repeats > 0 else (5 if args.full and args.steps < 100 else 1)
     pipe = bpipe = None
+    last = []
     if Bsz > 1:
         # stack mode: Bsz frames per submission through the same launches, S submissions in flight
         bpipe = BatchPipeline(model, dev, frames, Bsz, S, args.copy_inputs)
@@ -964,7 +1004,9 @@ def main():
     elif S == 1:
         def run1(nsteps):
             for i in range(nsteps):
-                one_step(model, frames[i % len(frames)])
+                out1, fxy1 = one_step(model, frames[i % len(frames)])
+            if nsteps:
+                last[:] = [(out1, fxy1)]
 
         for i in range(max(args.warmup, len(frames))):
             out, _ = one_step(model, frames[i % len(frames)])
@@ -975,6 +1017,8 @@ def main():
         nmatch = pipe.warm(args.warmup)
         dts = timed_repeats(pipe.run, barrier, args.steps, repeats)
     headline = bpipe if bpipe is not None else pipe
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, headline.last if headline is not None else last)
     dt = float(np.median(dts))   # this rank's seconds per timed region of args.steps steps
     peak_headline_gb = torch.cuda.max_memory_allocated(dev) / 2 ** 30   # weights + planes + inputs + one private pool per captured hipGraph
     gathered = per_rank = gather_ms = None
@@ -1039,7 +1083,7 @@ def main():
                                % ("KITTI-shape" if not args.stress else "stress (BASELINE configs[4])", Opt.img_H, Opt.img_W, args.points,
                                   "one frame (batch 1, BASELINE configs[1])" if Bsz == 1 else
                                   "one stack-mode batch of %d frames%s" % (Bsz, " (BASELINE configs[2])" if Bsz == 16 else ""), S,
-                                  "" if Bsz == 1 else "; the batch-1 pipeline (configs[1]) is in config.batch1_frames_per_s"),
+                                  "" if Bsz == 1 or not args.full else "; the batch-1 pipeline (configs[1]) is in config.batch1_frames_per_s"),
                    "batch": Bsz, "arithmetic": args.gemm,
                    "matches_per_frame": int(nmatch), "parallelism": "frame-parallel x%d" % world, "frame_streams_per_gpu": S,
                    "hipgraph_slots_per_stream": max(1, args.slots_per_stream) if (S > 1 and Bsz == 1) else 1},
@@ -1060,8 +1104,9 @@ def main():
         result["loader_leg"] = {"per_rank_frames_per_s": [r[0] for r in rates], "errors": [r[1] for r in rates if r[1]],
                                 "note": "FrameLoader (voxel grid + resample + KNN pyramid + image, nearest-only up-sampling tables) + forward + fine matching, "
                                         "pipelined, on every rank concurrently"}
-    extras = rank == 0 and world == 1 and not args.eager and not args.no_batch_sweep
-    if rank == 0 and world == 1 and not args.eager and S > 1 and not args.no_steady:
+    # everything below the headline is on record with --full only: a plain run stops at the result line
+    extras = args.full and rank == 0 and world == 1 and not args.eager and not args.no_batch_sweep
+    if args.full and rank == 0 and world == 1 and not args.eager and S > 1 and not args.no_steady:
         with optional_leg(result, "steady_state"):
             # the driver's 20 steps put a pipeline fill and drain inside a short timed region: the same loop over a longer one, on record
             nst = max(args.steps, (1600 + Bsz - 1) // Bsz if Bsz > 1 else 400)
@@ -1162,7 +1207,7 @@ def main():
                                                                          "note": "`from model.network import CoFiI2P`, nothing else changed"},
                                       "note": "model(pc_data_dict, img, ..., 'test') per frame as eval_all.py:94-96 calls it (hipGraph replay, one host "
                                               "sync per frame, no frames in flight); `value` is the pipelined forward_async / finish rate"}
-    if rank == 0 and not args.no_kernel_timing:
+    if args.full and rank == 0 and not args.no_kernel_timing:
         with optional_leg(result, "roofline"):
             model.enable_graphs(False)
             if Bsz == 1:
@@ -1222,7 +1267,7 @@ def main():
                     model.enable_graphs(True)
                 del pyr_b, img_b
             result["stack_mode_batches"] = sweep
-    if rank == 0 and world == 1 and not args.no_batch_sweep:
+    if args.full and rank == 0 and world == 1 and not args.no_batch_sweep:
         with optional_leg(result, "knn_pyramid"):
             # additional information, outside `value` (the reference's DataLoader builds the pyramid, preprocess_data.py:36-107): the 13
             # KNN-128 searches of one frame's pyramid on this GPU, cell-grid search vs the brute-force kernel (identical tables)
@@ -1383,14 +1428,14 @@ def main():
     if extras and not args.stress:
         with optional_leg(result, "stress_config"):
             result["stress_config"] = stress_summary(dev, args)
-    if rank == 0 and world == 1 and not args.no_batch_sweep and not args.stress:
+    if args.full and rank == 0 and world == 1 and not args.no_batch_sweep and not args.stress:
         # row f3, outside `value`: one optimisation step of train.py:186-286 on the same frame (forward(mode='train') -> the three losses ->
         # backward -> Adam), fp32-grade contractions (bf16x6); a separate module instance so the served one keeps its weights
         try:
             result["train_step"] = train_step_summary(dev, frames[0])
         except Exception as e:   # additional information only: never costs the line
             result["train_step"] = {"error": "%s: %s" % (type(e).__name__, e)}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         with optional_leg(result, "cpu_baseline"):
             result["cpu_baseline"] = cpu_baseline(frames[0])
     if rank == 0:

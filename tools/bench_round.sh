@@ -6,7 +6,7 @@ R=$GRAFT_REPO_ROOT
 OUT=$R/gpurun_out/$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-python $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline > $OUT/bench_driver.json 2> $OUT/bench_driver.err
+python $R/bench.py --steps 20 --warmup 5 --full --no-cpu-baseline > $OUT/bench_driver.json 2> $OUT/bench_driver.err
 python $R/bench.py --no-cpu-baseline --no-kernel-timing --no-batch-sweep > $OUT/bench_200.json 2> $OUT/bench_200.err
 if [ "${2:-}" = "trace" ]; then
   BENCH="python $R/bench.py --steps 20 --warmup 4 --no-cpu-baseline --no-kernel-timing --no-batch-sweep"

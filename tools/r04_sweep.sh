@@ -10,7 +10,7 @@ for cfg in "1 4" "2 4" "4 2" "4 4" "8 2" "8 4" "16 2" "16 4"; do
   set -- $cfg; B=$1; S=$2
   steps=$(( 256 / B )); [ $steps -lt 12 ] && steps=12
   extra="--no-kernel-timing"; [ "$S" = "2" ] && extra=""
-  python $R/bench.py --no-cpu-baseline --no-batch-sweep --no-f32 $extra --gemm $M --batch $B --inflight $S --steps $steps > $OUT/b${B}_s${S}.json 2> $OUT/b${B}_s${S}.err
+  python $R/bench.py --full --no-cpu-baseline --no-batch-sweep --no-f32 $extra --gemm $M --batch $B --inflight $S --steps $steps > $OUT/b${B}_s${S}.json 2> $OUT/b${B}_s${S}.err
   python - <<PY
 import json
 d = json.loads(open("$OUT/b${B}_s${S}.json").read().strip().splitlines()[-1])
