@@ -12,6 +12,11 @@
 //   the winner is the hypothesis with most inliers, lowest id on ties - deterministic.
 // Kernel 2: one workgroup refits the winner on its inliers: LM on the reprojection error with left-multiplied se(3) increments,
 //   normal equations reduced in a fixed order (fp64), 6x6 solve by one thread.
+// Both kernels exist in two forms around ONE body each (hypotheses_wave, refine_workgroup): per frame (cofi_pnp_ransac), and batched
+//   (cofi_pnp_ransac_batch: frame on the grid, operands addressed through strides, count and intrinsics read on the device; a workgroup
+//   of 4 waves stages its frame's correspondences once in LDS and its 64 hypotheses score from there).  The bodies receive VALUES through
+//   an accessor, so frame f of a batch executes the arithmetic of the per-frame call in the same order: bit-identical results.
+// Kernel 3 (pose_errors_kernel): RTE / RRE of B poses against ground truth, one thread per frame, fp64.
 #include "common.h"
 
 namespace {
@@ -173,13 +178,32 @@ __device__ __forceinline__ bool inlier(const float p[12], const float *X, const 
     return y2 > 1e-6f && eu * eu + ev * ev <= thr2;
 }
 
-__global__ __launch_bounds__(64) void pnp_hypotheses_kernel(const float *obj, const float *img, const int32_t *count_dev, int n_max, Cam cam,
-                                                            int iters, float thr2, unsigned seed, float *poses,
-                                                            unsigned long long *best_key) {
-    const int lane = threadIdx.x;
-    const int n = count_dev ? min(*count_dev, n_max) : n_max;
-    if (n < 4) return;
-    const int hyp = blockIdx.x * HPW + lane;
+// Where a kernel finds correspondence i.  Every kernel below takes one of these and hands VALUES (X[3], uv[2]) to the shared device
+// functions, so the per-frame and the batched kernels execute the same arithmetic whatever the operand layout.
+struct CorrGlobal {   // global memory: object point i at obj[3 i ..], pixel i at (u[i * step], v[i * step])
+    const float *obj, *u, *v;
+    int step;         // 2: point-major (n, 2) with v = u + 1;  1: coordinate-major (2, n) with v = u + n_max
+    __device__ __forceinline__ void load(int i, float X[3], float uv[2]) const {
+        X[0] = obj[3 * i]; X[1] = obj[3 * i + 1]; X[2] = obj[3 * i + 2];
+        uv[0] = u[(size_t)i * step]; uv[1] = v[(size_t)i * step];
+    }
+};
+struct CorrLds {      // structure of arrays in LDS, `ld` floats apart: x | y | z | u | v (20 bytes per correspondence, conflict-free strides)
+    const float *s;
+    int ld;
+    __device__ __forceinline__ void load(int i, float X[3], float uv[2]) const {
+        X[0] = s[i]; X[1] = s[ld + i]; X[2] = s[2 * ld + i];
+        uv[0] = s[3 * ld + i]; uv[1] = s[4 * ld + i];
+    }
+};
+
+// One wave, HPW hypotheses hyp0 .. hyp0 + HPW - 1 (lane h < HPW solves hypothesis hyp0 + h, then all 64 lanes score the HPW poses one
+// after the other).  The body of both hypotheses kernels.
+template <class Corr>
+__device__ __forceinline__ void hypotheses_wave(const Corr &corr, int n, const Cam &cam, int iters, float thr2, unsigned seed, int hyp0,
+                                                float *poses, unsigned long long *best_key) {
+    const int lane = threadIdx.x & 63;
+    const int hyp = hyp0 + lane;
     float pose_f[12];
     bool ok = false;
     if (lane < HPW && hyp < iters) {
@@ -195,15 +219,18 @@ __global__ __launch_bounds__(64) void pnp_hypotheses_kernel(const float *obj, co
             idx[j] = c;
         }
         double X[3][3], f[3][3];
+        float Xf[3], uvf[2];
         for (int k = 0; k < 3; ++k) {
-            for (int e = 0; e < 3; ++e) X[k][e] = (double)obj[3 * idx[k] + e];
-            const double bx = ((double)img[2 * idx[k]] - cam.cx) / cam.fx, by = ((double)img[2 * idx[k] + 1] - cam.cy) / cam.fy;
+            corr.load(idx[k], Xf, uvf);
+            for (int e = 0; e < 3; ++e) X[k][e] = (double)Xf[e];
+            const double bx = ((double)uvf[0] - cam.cx) / cam.fx, by = ((double)uvf[1] - cam.cy) / cam.fy;
             const double inv = 1.0 / sqrt(bx * bx + by * by + 1.0);
             f[k][0] = bx * inv; f[k][1] = by * inv; f[k][2] = inv;
         }
-        const double X4[3] = {(double)obj[3 * idx[3]], (double)obj[3 * idx[3] + 1], (double)obj[3 * idx[3] + 2]};
+        corr.load(idx[3], Xf, uvf);
+        const double X4[3] = {(double)Xf[0], (double)Xf[1], (double)Xf[2]};
         double pose[12];
-        ok = p3p_pick(X, f, X4, (double)img[2 * idx[3]], (double)img[2 * idx[3] + 1], cam, pose);
+        ok = p3p_pick(X, f, X4, (double)uvf[0], (double)uvf[1], cam, pose);
         if (ok)
             for (int k = 0; k < 12; ++k) {
                 pose_f[k] = (float)pose[k];
@@ -218,12 +245,68 @@ __global__ __launch_bounds__(64) void pnp_hypotheses_kernel(const float *obj, co
 #pragma unroll
         for (int k = 0; k < 12; ++k) p[k] = __shfl(pose_f[k], h, 64);
         int cnt = 0;
-        for (int i = lane; i < n; i += 64) cnt += inlier(p, obj + 3 * i, img + 2 * i, cam, thr2) ? 1 : 0;
+        for (int i = lane; i < n; i += 64) {
+            float Xi[3], uvi[2];
+            corr.load(i, Xi, uvi);
+            cnt += inlier(p, Xi, uvi, cam, thr2) ? 1 : 0;
+        }
         for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o, 64);
-        const unsigned long long key = ((unsigned long long)(unsigned)cnt << 32) | (unsigned long long)(0xFFFFFFFFu - (unsigned)(blockIdx.x * HPW + h));
+        const unsigned long long key = ((unsigned long long)(unsigned)cnt << 32) | (unsigned long long)(0xFFFFFFFFu - (unsigned)(hyp0 + h));
         wave_best = key > wave_best ? key : wave_best;
     }
     if (lane == 0 && wave_best) atomicMax(best_key, wave_best);
+}
+
+__global__ __launch_bounds__(64) void pnp_hypotheses_kernel(const float *obj, const float *img, const int32_t *count_dev, int n_max, Cam cam,
+                                                            int iters, float thr2, unsigned seed, float *poses,
+                                                            unsigned long long *best_key) {
+    const int n = count_dev ? min(*count_dev, n_max) : n_max;
+    if (n < 4) return;
+    hypotheses_wave(CorrGlobal{obj, img, img + 1, 2}, n, cam, iters, thr2, seed, blockIdx.x * HPW, poses, best_key);
+}
+
+// ---- the batched form: frame on blockIdx.y, operands addressed through strides, intrinsics and counts read on the device
+struct BatchOperands {
+    const float *obj;          // frame f: obj + f * obj_stride, (n_max, 3)
+    const float *img;          // frame f: img + f * img_stride; (n_max, 2), or (2, n_max) if coord_major
+    const int32_t *count;      // frame f: count[f * count_stride] valid rows (NULL: n_max)
+    const float *K;            // (frames, 3, 3) row-major
+    int obj_stride, img_stride, count_stride, coord_major, n_max;
+    __device__ __forceinline__ int rows(int f) const { return count ? min(count[(size_t)f * count_stride], n_max) : n_max; }
+    __device__ __forceinline__ Cam cam(int f) const { return Cam{K[9 * f], K[9 * f + 4], K[9 * f + 2], K[9 * f + 5]}; }
+    __device__ __forceinline__ CorrGlobal corr(int f) const {
+        const float *uv = img + (size_t)f * img_stride;
+        return CorrGlobal{obj + (size_t)f * obj_stride, uv, coord_major ? uv + n_max : uv + 1, coord_major ? 1 : 2};
+    }
+};
+
+constexpr int BATCH_WAVES = 4;   // waves per workgroup of the batched hypotheses kernel: 64 hypotheses share one staged copy of the frame
+
+// LDS = true: the workgroup stages its frame's correspondences once in LDS (5 n_max floats, dynamic) and every hypothesis scores from
+// there; false (frames too large for 64 KiB): from global memory, as the per-frame kernel does.  Same values either way.
+template <bool LDS>
+__global__ __launch_bounds__(64 * BATCH_WAVES) void pnp_hypotheses_batch_kernel(BatchOperands op, int iters, float thr2, unsigned seed,
+                                                                                float *poses, unsigned long long *best_keys) {
+    extern __shared__ float s_corr[];
+    const int f = blockIdx.y;
+    const int n = op.rows(f);
+    const Cam cam = op.cam(f);
+    if (n < 4 || !(cam.fx > 0.f) || !(cam.fy > 0.f)) return;   // frame-uniform: the key stays 0 and the refit reports failure
+    const CorrGlobal g = op.corr(f);
+    const int hyp0 = (blockIdx.x * BATCH_WAVES + (threadIdx.x >> 6)) * HPW;
+    float *slab = poses + (size_t)f * iters * 12;
+    if (LDS) {
+        for (int i = threadIdx.x; i < n; i += 64 * BATCH_WAVES) {
+            float X[3], uv[2];
+            g.load(i, X, uv);
+            s_corr[i] = X[0]; s_corr[op.n_max + i] = X[1]; s_corr[2 * op.n_max + i] = X[2];
+            s_corr[3 * op.n_max + i] = uv[0]; s_corr[4 * op.n_max + i] = uv[1];
+        }
+        __syncthreads();
+        hypotheses_wave(CorrLds{s_corr, op.n_max}, n, cam, iters, thr2, seed + (unsigned)f, hyp0, slab, best_keys + f);
+    } else {
+        hypotheses_wave(g, n, cam, iters, thr2, seed + (unsigned)f, hyp0, slab, best_keys + f);
+    }
 }
 
 // ---- refit: Levenberg-Marquardt on the inliers of the winning hypothesis
@@ -246,16 +329,16 @@ __device__ void accumulate(const double R[9], const double t[3], const float *X,
     acc[27] += r0 * r0 + r1 * r1;
 }
 
-__global__ __launch_bounds__(256) void pnp_refine_kernel(const float *obj, const float *img, const int32_t *count_dev, int n_max, Cam cam,
-                                                         float thr2, const float *poses, const unsigned long long *best_key, int lm_iters,
-                                                         float *pose_out, int32_t *result /* [0] success, [1] inliers, [2] hypothesis */,
-                                                         uint8_t *mask) {
+// One workgroup of 256 threads refits one frame.  The body of both refit kernels.
+template <class Corr>
+__device__ __forceinline__ void refine_workgroup(const Corr &corr, int n, int n_max, const Cam &cam, float thr2, const float *poses,
+                                                 const unsigned long long *best_key, int lm_iters, float *pose_out,
+                                                 int32_t *result /* [0] success, [1] inliers, [2] hypothesis */, uint8_t *mask) {
     __shared__ double s_red[4][NACC];
     __shared__ double s_sys[NACC];     // reduced normal equations of the candidate pose
     __shared__ double s_pose[12], s_cand[12];
     __shared__ int s_cnt[4];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    const int n = count_dev ? min(*count_dev, n_max) : n_max;
     const unsigned long long key = *best_key;
     const int cnt_best = (int)(key >> 32);
     const int hyp = (int)(0xFFFFFFFFu - (unsigned)(key & 0xFFFFFFFFull));
@@ -273,7 +356,9 @@ __global__ __launch_bounds__(256) void pnp_refine_kernel(const float *obj, const
     // inlier mask of the RANSAC model (what cv2 returns as `inliers`)
     int c = 0;
     for (int i = tid; i < n; i += 256) {
-        const bool in = inlier(pf, obj + 3 * i, img + 2 * i, cam, thr2);
+        float Xi[3], uvi[2];
+        corr.load(i, Xi, uvi);
+        const bool in = inlier(pf, Xi, uvi, cam, thr2);
         mask[i] = in ? 1 : 0;
         c += in ? 1 : 0;
     }
@@ -290,7 +375,11 @@ __global__ __launch_bounds__(256) void pnp_refine_kernel(const float *obj, const
         for (int k = 0; k < 9; ++k) R[k] = pose[k];
         for (int k = 0; k < 3; ++k) t[k] = pose[9 + k];
         for (int i = tid; i < n; i += 256)
-            if (mask[i]) accumulate(R, t, obj + 3 * i, img + 2 * i, cam, acc);
+            if (mask[i]) {
+                float Xi[3], uvi[2];
+                corr.load(i, Xi, uvi);
+                accumulate(R, t, Xi, uvi, cam, acc);
+            }
         for (int k = 0; k < NACC; ++k) {
             const double v = wave_sum_d(acc[k]);
             if (lane == 0) s_red[wv][k] = v;
@@ -374,6 +463,80 @@ __global__ __launch_bounds__(256) void pnp_refine_kernel(const float *obj, const
     }
 }
 
+__global__ __launch_bounds__(256) void pnp_refine_kernel(const float *obj, const float *img, const int32_t *count_dev, int n_max, Cam cam,
+                                                         float thr2, const float *poses, const unsigned long long *best_key, int lm_iters,
+                                                         float *pose_out, int32_t *result, uint8_t *mask) {
+    const int n = count_dev ? min(*count_dev, n_max) : n_max;
+    refine_workgroup(CorrGlobal{obj, img, img + 1, 2}, n, n_max, cam, thr2, poses, best_key, lm_iters, pose_out, result, mask);
+}
+
+// frame f = blockIdx.x: pose_out (frames, 12), result (frames, 3), mask (frames, n_max).  A frame the hypotheses kernel left at once
+// (count < 4, unusable intrinsics) has key 0 and takes the failure exit.
+__global__ __launch_bounds__(256) void pnp_refine_batch_kernel(BatchOperands op, int iters, float thr2, const float *poses,
+                                                               const unsigned long long *best_keys, int lm_iters, float *pose_out,
+                                                               int32_t *result, uint8_t *mask) {
+    const int f = blockIdx.x;
+    refine_workgroup(op.corr(f), op.rows(f), op.n_max, op.cam(f), thr2, poses + (size_t)f * iters * 12, best_keys + f, lm_iters,
+                     pose_out + 12 * f, result + 3 * f, mask + (size_t)f * op.n_max);
+}
+
+// ---- registration errors of B poses (evaluation/eval_all.py:16-22): P_diff = inv(P_pred) P_gt, RTE = |t|, RRE = sum |euler 'xzy'| in degrees
+template <class T>
+__global__ __launch_bounds__(64) void pose_errors_kernel(const float *pose, const T *P_gt, int frames, double *out) {
+    const int f = blockIdx.x * 64 + threadIdx.x;
+    if (f >= frames) return;
+    // [P_pred | I] -> [I | inv(P_pred)]: Gauss-Jordan with partial pivoting, fp64.  A general inverse: the refit's R is orthonormal to fp32 only.
+    double A[4][8];
+    for (int r = 0; r < 4; ++r)
+        for (int c = 0; c < 8; ++c) A[r][c] = c < 4 ? (r == c ? 1.0 : 0.0) : (c - 4 == r ? 1.0 : 0.0);
+    for (int r = 0; r < 3; ++r) {
+        for (int c = 0; c < 3; ++c) A[r][c] = (double)pose[12 * f + 3 * r + c];
+        A[r][3] = (double)pose[12 * f + 9 + r];
+    }
+    bool ok = true;
+    for (int col = 0; col < 4; ++col) {
+        int piv = col;
+        for (int r = col + 1; r < 4; ++r)
+            if (fabs(A[r][col]) > fabs(A[piv][col])) piv = r;
+        if (!(fabs(A[piv][col]) > 0.0)) { ok = false; break; }
+        if (piv != col)
+            for (int j = 0; j < 8; ++j) { const double tmp = A[col][j]; A[col][j] = A[piv][j]; A[piv][j] = tmp; }
+        const double d = A[col][col];
+        for (int j = 0; j < 8; ++j) A[col][j] /= d;
+        for (int r = 0; r < 4; ++r) {
+            if (r == col) continue;
+            const double fct = A[r][col];
+            for (int j = 0; j < 8; ++j) A[r][j] -= fct * A[col][j];
+        }
+    }
+    if (!ok) {   // singular P_pred: no error is defined
+        out[2 * f] = out[2 * f + 1] = __builtin_nan("");
+        return;
+    }
+    double D[3][4];   // the three rows of P_diff the errors read
+    for (int r = 0; r < 3; ++r)
+        for (int c = 0; c < 4; ++c) {
+            double acc = 0.0;
+            for (int k = 0; k < 4; ++k) acc += A[r][4 + k] * (double)P_gt[16 * f + 4 * k + c];
+            D[r][c] = acc;
+        }
+    const double rte = sqrt(D[0][3] * D[0][3] + D[1][3] * D[1][3] + D[2][3] * D[2][3]);
+    // scipy's as_euler('xzy') as pose.euler_xzy_deg restates it: R = Ry(c) Rz(b) Rx(a); gimbal lock: third angle zero
+    const double s = D[1][0];
+    const double b = asin(s > 1.0 ? 1.0 : (s < -1.0 ? -1.0 : s));
+    double a, c;
+    if (fabs(s) < 1.0 - 1e-12) {
+        a = atan2(-D[1][2], D[1][1]);
+        c = atan2(-D[2][0], D[0][0]);
+    } else {
+        a = atan2(D[2][1], D[2][2]);
+        c = 0.0;
+    }
+    const double deg = 180.0 / 3.14159265358979323846;
+    out[2 * f] = rte;
+    out[2 * f + 1] = fabs(a * deg) + fabs(b * deg) + fabs(c * deg);
+}
+
 }  // namespace
 
 extern "C" size_t cofi_pnp_ransac_workspace(int iterations) {
@@ -396,5 +559,47 @@ extern "C" int cofi_pnp_ransac(const float *obj, const float *img, const int32_t
                        reproj_err * reproj_err, seed, poses, key);
     hipLaunchKernelGGL(pnp_refine_kernel, dim3(1), dim3(256), 0, s, obj, img, count_dev, n_max, cam, reproj_err * reproj_err, poses, key,
                        refine_iters, pose, result, inlier_mask);
+    return cofi_launch_status();
+}
+
+// workspace of the batched call: one consensus key per frame (padded to 64 bytes), then one slab of iterations x 12 floats per frame
+static size_t batch_key_bytes(int frames) { return ((size_t)frames * 8 + 63) / 64 * 64; }
+
+extern "C" size_t cofi_pnp_ransac_batch_workspace(int iterations, int frames) {
+    return iterations > 0 && frames > 0 ? batch_key_bytes(frames) + (size_t)frames * iterations * 12 * sizeof(float) : 0;
+}
+
+extern "C" int cofi_pnp_ransac_batch(const float *obj, int obj_frame_stride, const float *img, int img_frame_stride, int coord_major,
+                                     const int32_t *count_dev, int count_stride, const float *K_dev, int n_max, int frames, int iterations,
+                                     float reproj_err, unsigned seed, int refine_iters, void *ws, size_t ws_bytes, float *pose,
+                                     int32_t *result, uint8_t *inlier_mask, cofi_stream_t stream) {
+    if (!obj || !img || !K_dev || !pose || !result || !inlier_mask || n_max <= 0 || frames <= 0 || frames > 65535 || iterations <= 0 ||
+        !(reproj_err > 0.f) || refine_iters < 0 || obj_frame_stride < 3 * n_max || img_frame_stride < 2 * n_max || (count_dev && count_stride < 1))
+        return COFI_EINVAL;
+    if (!ws || ws_bytes < cofi_pnp_ransac_batch_workspace(iterations, frames) || ((uintptr_t)ws & 15)) return COFI_EWORKSPACE;
+    hipStream_t s = cofi_s(stream);
+    unsigned long long *keys = (unsigned long long *)ws;
+    float *poses = (float *)((char *)ws + batch_key_bytes(frames));
+    if (hipError_t e = hipMemsetAsync(keys, 0, batch_key_bytes(frames), s); e != hipSuccess) return (int)e;
+    const BatchOperands op{obj, img, count_dev, K_dev, obj_frame_stride, img_frame_stride, count_stride, coord_major ? 1 : 0, n_max};
+    const float thr2 = reproj_err * reproj_err;
+    const dim3 grid(cofi_cdiv(iterations, HPW * BATCH_WAVES), frames), block(64 * BATCH_WAVES);
+    const size_t lds = (size_t)n_max * 5 * sizeof(float);
+    if (lds <= 64 * 1024)
+        hipLaunchKernelGGL(pnp_hypotheses_batch_kernel<true>, grid, block, lds, s, op, iterations, thr2, seed, poses, keys);
+    else
+        hipLaunchKernelGGL(pnp_hypotheses_batch_kernel<false>, grid, block, 0, s, op, iterations, thr2, seed, poses, keys);
+    hipLaunchKernelGGL(pnp_refine_batch_kernel, dim3(frames), dim3(256), 0, s, op, iterations, thr2, poses, keys, refine_iters, pose, result,
+                       inlier_mask);
+    return cofi_launch_status();
+}
+
+extern "C" int cofi_pose_errors(const float *pose, const void *P_gt, int gt_is_f64, int frames, double *out, cofi_stream_t stream) {
+    if (!pose || !P_gt || !out || frames <= 0) return COFI_EINVAL;
+    hipStream_t s = cofi_s(stream);
+    if (gt_is_f64)
+        hipLaunchKernelGGL(pose_errors_kernel<double>, dim3(cofi_cdiv(frames, 64)), dim3(64), 0, s, pose, (const double *)P_gt, frames, out);
+    else
+        hipLaunchKernelGGL(pose_errors_kernel<float>, dim3(cofi_cdiv(frames, 64)), dim3(64), 0, s, pose, (const float *)P_gt, frames, out);
     return cofi_launch_status();
 }

@@ -332,6 +332,8 @@ class CoFiI2P(nn.Module):
             outs.append(o)
         if test:
             outs[0]["count_all"] = cnt   # (B, 2): one device-to-host copy serves every frame of the submission
+            if C2 <= 128:   # what a batched consumer of the matches reads in place (pose.solve_pnp_ransac_batch): (B, cap, 3), (B, 2, cap)
+                outs[0]["coarse_pts_all"], outs[0]["fine_xy_all"] = cpts, fxy
         br_dead.join()
         return outs
 
@@ -455,7 +457,8 @@ class CoFiI2P(nn.Module):
         return (pool + extra)[:n]
 
     @torch.no_grad()
-    def forward_async(self, slot: int, pc_data_dict, img, mode: str = "test", inputs_stable: bool = False):
+    def forward_async(self, slot: int, pc_data_dict, img, mode: str = "test", inputs_stable: bool = False, pose_K=None,
+                      pose_iterations: int = 10000, pose_seed: int = 0):
         """Enqueue one test-mode forward on the CURRENT stream through the hipGraph of slot `slot` and return
         immediately (no host sync).  `img` (1,3,H,W) = one frame, or (B,3,H,W) with a stack-mode `pc_data_dict`
         (see stack_frames) = B frames through the same launches.  Slots own their static buffers and scratch, so
@@ -466,14 +469,50 @@ class CoFiI2P(nn.Module):
         so any tensors may be passed.  inputs_stable=True: the caller promises that these very tensors (contiguous, device-resident,
         int32 tables) stay allocated and unmodified until `finish()`; the graph then reads them IN PLACE - no staging copy - and is
         cached per (slot, input addresses): the natural mode for a loader that recycles a ring of input buffers
-        (at most MAX_STABLE_GRAPHS distinct sets)."""
+        (at most MAX_STABLE_GRAPHS distinct sets).
+
+        pose_K (camera matrices, (B,3,3) or one (3,3) for all frames; host or device): the pose of every frame is solved behind the
+        forward on the same stream (pose.solve_pnp_ransac_batch reading the submission's coarse points, coordinate-major fine_xy and
+        device-side counts in place; frame f uses seed pose_seed + f) and the handle gains handle["pose"] = {"result" (B,3) int32,
+        "R" (B,3,3), "t" (B,3), "inliers" (B,cap) uint8}: device tensors owned by the slot, valid like the other outputs until the slot
+        is reused, and complete when `finish(handle)` returns.  A float32 device (B,3,3) pose_K is read in place (keep it unmodified
+        until `finish()`); anything else is copied into a buffer of the slot."""
         if mode != "test":
             raise ValueError("forward_async serves the test-mode pipeline")
         _lib.load()
         with ops.arithmetic(self.arithmetic):
-            return self._forward_async(slot, pc_data_dict, img, mode, inputs_stable)
+            return self._forward_async(slot, pc_data_dict, img, mode, inputs_stable, pose_K, pose_iterations, pose_seed)
 
-    def _forward_async(self, slot, pc_data_dict, img, mode, inputs_stable):
+    def _enqueue_pose(self, slot, outs, K, iterations, seed):
+        """the batched pose tail of a submission, on the current stream, into buffers the slot owns"""
+        from . import pose as _pose
+
+        if "coarse_pts_all" not in outs[0]:
+            raise _lib.CofiError("forward_async(pose_K=...): the batched pose tail reads the outputs of match_finish, which serves fine "
+                                 "feature maps of at most 128 channels; this model's fine map is wider")
+        cpts, fxy, cnt = outs[0]["coarse_pts_all"], outs[0]["fine_xy_all"], outs[0]["count_all"]
+        B, cap, dev = cpts.shape[0], cpts.shape[1], cpts.device
+        if not torch.is_tensor(K):
+            K = torch.as_tensor(np.asarray(K, dtype=np.float32))
+        if tuple(K.shape) not in ((B, 3, 3), (3, 3)):
+            raise _lib.CofiError("forward_async: pose_K must be (B,3,3) = %s or (3,3), got %s" % ((B, 3, 3), tuple(K.shape)))
+        bufs = self.__dict__.setdefault("_pose_bufs", {})
+        key = (slot, B, cap, int(iterations), str(dev))
+        b = bufs.get(key)
+        if b is None:
+            b = bufs[key] = {"ws": torch.empty(_pose.pnp_batch_workspace(iterations, B), dtype=torch.uint8, device=dev),
+                             "pose": torch.empty((B, 12), dtype=torch.float32, device=dev),
+                             "result": torch.empty((B, 3), dtype=torch.int32, device=dev),
+                             "mask": torch.empty((B, cap), dtype=torch.uint8, device=dev),
+                             "K": torch.empty((B, 3, 3), dtype=torch.float32, device=dev)}
+        if not (K.is_cuda and K.device == dev and K.dtype == torch.float32 and K.dim() == 3 and K.is_contiguous()):
+            b["K"].copy_(K, non_blocking=True)   # broadcasts a (3,3); a device K of another dtype is converted on the device
+            K = b["K"]
+        res, R, t, mask = _pose.solve_pnp_ransac_batch_into(cpts, fxy, K, cnt[:, 0], b["ws"], b["pose"], b["result"], b["mask"],
+                                                            iterations=iterations, seed=seed, coord_major=True)
+        return {"result": res, "R": R, "t": t, "inliers": mask}
+
+    def _forward_async(self, slot, pc_data_dict, img, mode, inputs_stable, pose_K=None, pose_iterations=10000, pose_seed=0):
         P = self._pack(img.device)
         if inputs_stable:
             for k in ("points", "neighbors", "subsampling", "upsampling"):
@@ -494,9 +533,13 @@ class CoFiI2P(nn.Module):
         if host is None:
             host = hosts[(slot, len(outs))] = torch.empty((len(outs), 2), dtype=torch.int32, pin_memory=True)
         host.copy_(outs[0]["count_all"], non_blocking=True)
+        pose = None if pose_K is None else self._enqueue_pose(slot, outs, pose_K, pose_iterations, pose_seed)
         done = torch.cuda.Event()
         done.record()
-        return {"out": outs, "count_host": host, "done": done}
+        handle = {"out": outs, "count_host": host, "done": done}
+        if pose is not None:
+            handle["pose"] = pose
+        return handle
 
     def _slice_result(self, o, n: int, thr_i: int):
         if thr_i < 0:

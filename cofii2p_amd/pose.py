@@ -7,7 +7,11 @@
 `solve_pnp_ransac` runs on the device (cofi_pnp_ransac: P3P hypotheses in parallel, consensus by reprojection error, LM refit);
 its arguments are CUDA tensors and nothing is copied to the host unless the caller asks for `ok`.  OpenCV is not available in
 this environment, so equality with cv2's result is not pinned; the implementation is checked against
-oracle/pnp_oracle.py and against ground-truth poses of synthetic correspondences."""
+oracle/pnp_oracle.py and against ground-truth poses of synthetic correspondences.
+
+For the B frames of a stack-mode submission: `solve_pnp_ransac_batch` (cofi_pnp_ransac_batch: all frames in two launches, operands and
+intrinsics read on the device in the layout the forward leaves them, frame f bit-identical to the per-frame call with seed + f) and
+`pose_errors` (cofi_pose_errors: get_P_diff of B poses on the device)."""
 from typing import Optional
 
 import numpy as np
@@ -40,6 +44,104 @@ def solve_pnp_ransac(object_points: torch.Tensor, image_points: torch.Tensor, K,
                              int(refine_iters), ops._p(ws), ws.numel(), ops._p(pose), ops._p(result), ops._p(mask), ops._stream())
     _lib.check(rc, "cofi_pnp_ransac")
     return result, pose[:9].view(3, 3), pose[9:], mask
+
+
+def _batch_operands(object_points, image_points, K, count, coord_major, what):
+    """checks of the batched call -> (B, cap, K on the device, count pointer, count stride)"""
+    E = _lib.CofiError
+    if not (torch.is_tensor(object_points) and object_points.is_cuda and object_points.dtype == torch.float32 and object_points.dim() == 3
+            and object_points.shape[2] == 3 and object_points.is_contiguous()):
+        raise E("%s: object_points must be a contiguous CUDA float32 (B,cap,3) tensor" % what)
+    B, cap = object_points.shape[0], object_points.shape[1]
+    want = (B, 2, cap) if coord_major else (B, cap, 2)
+    if not (torch.is_tensor(image_points) and image_points.is_cuda and image_points.dtype == torch.float32 and tuple(image_points.shape) == want
+            and image_points.is_contiguous()):
+        raise E("%s: image_points must be a contiguous CUDA float32 %s tensor (coord_major=%s)" % (what, want, bool(coord_major)))
+    if B == 0 or cap == 0:
+        raise E("%s: need B >= 1 frames of capacity >= 1" % what)
+    dev = object_points.device
+    if not torch.is_tensor(K):
+        K = torch.as_tensor(np.asarray(K, dtype=np.float32))
+    if tuple(K.shape) != (B, 3, 3):
+        raise E("%s: K must be (B,3,3) = %s, got %s" % (what, (B, 3, 3), tuple(K.shape)))
+    if K.is_cuda:   # read in place by the kernels: never copied to the host
+        if K.dtype != torch.float32 or not K.is_contiguous() or K.device != dev:
+            raise E("%s: a device K must be a contiguous float32 tensor on the device of the points" % what)
+    else:
+        K = K.to(torch.float32).contiguous().to(dev, non_blocking=True)
+    cstride = 0
+    if count is not None:
+        if not (torch.is_tensor(count) and count.is_cuda and count.dtype == torch.int32 and count.dim() == 1 and count.shape[0] == B
+                and (B == 1 or count.stride(0) >= 1)):
+            raise E("%s: count must be an int32 CUDA tensor of B elements (a strided 1-D view is read in place)" % what)
+        cstride = max(1, count.stride(0))
+    return B, cap, K, count, cstride
+
+
+def pnp_batch_workspace(iterations: int, frames: int) -> int:
+    return _lib.load().cofi_pnp_ransac_batch_workspace(int(iterations), int(frames))
+
+
+def solve_pnp_ransac_batch_into(object_points, image_points, K, count, ws, pose, result, mask, iterations: int = 10000,
+                                reproj_error: float = 8.0, seed: int = 0, refine_iters: int = 20, coord_major: bool = False):
+    """solve_pnp_ransac_batch into caller-owned buffers (ws uint8, pose (B,12) float32, result (B,3) int32, mask (B,cap) uint8): the
+    form a pipeline with static buffers uses.  Enqueues a memset and two kernels on the current stream; nothing else."""
+    lib = _lib.load()
+    B, cap, K, count, cstride = _batch_operands(object_points, image_points, K, count, coord_major, "solve_pnp_ransac_batch")
+    for t_, shape, dt in ((pose, (B, 12), torch.float32), (result, (B, 3), torch.int32), (mask, (B, cap), torch.uint8)):
+        if not (t_.is_cuda and t_.dtype == dt and tuple(t_.shape) == shape and t_.is_contiguous()):
+            raise _lib.CofiError("solve_pnp_ransac_batch: output buffers must be contiguous CUDA tensors pose (B,12) float32, result (B,3) int32, mask (B,cap) uint8")
+    rc = lib.cofi_pnp_ransac_batch(ops._p(object_points), 3 * cap, ops._p(image_points), 2 * cap, 1 if coord_major else 0, ops._p(count), cstride,
+                                   ops._p(K), cap, B, int(iterations), float(reproj_error), int(seed) & 0xFFFFFFFF, int(refine_iters),
+                                   ops._p(ws), ws.numel(), ops._p(pose), ops._p(result), ops._p(mask), ops._stream())
+    _lib.check(rc, "cofi_pnp_ransac_batch")
+    return result, pose[:, :9].view(B, 3, 3), pose[:, 9:], mask
+
+
+def solve_pnp_ransac_batch(object_points: torch.Tensor, image_points: torch.Tensor, K, count: Optional[torch.Tensor] = None,
+                           iterations: int = 10000, reproj_error: float = 8.0, seed: int = 0, refine_iters: int = 20,
+                           coord_major: bool = False):
+    """The pose of every frame of a stack-mode submission in one pass (cofi_pnp_ransac_batch): frame f is bit-identical to
+    solve_pnp_ransac(object_points[f, :n_f], image_points[f, :n_f], K[f], seed=seed + f).
+
+    object_points (B,cap,3); image_points (B,cap,2), or (B,2,cap) with coord_major=True (the `fine_xy` the forward writes: no
+    transpose); K (B,3,3): a float32 device tensor is read by the kernels in place, a host tensor / array is uploaded - the intrinsics
+    never travel to the host; count: int32 device tensor of B valid-row counts, possibly a strided view such as count_all[:, 0]
+    (None: every row of every frame is valid).  Returns (result (B,3) int32 [success, inliers, winning hypothesis], R (B,3,3), t (B,3),
+    inlier_mask (B,cap) uint8) as device tensors.  No host synchronisation: the call can be captured in a hipGraph."""
+    B, cap, K, count, _ = _batch_operands(object_points, image_points, K, count, coord_major, "solve_pnp_ransac_batch")
+    dev = object_points.device
+    ws = torch.empty(pnp_batch_workspace(iterations, B), dtype=torch.uint8, device=dev)
+    pose = torch.empty((B, 12), dtype=torch.float32, device=dev)
+    result = torch.empty((B, 3), dtype=torch.int32, device=dev)
+    mask = torch.empty((B, cap), dtype=torch.uint8, device=dev)
+    return solve_pnp_ransac_batch_into(object_points, image_points, K, count, ws, pose, result, mask, iterations, reproj_error, seed,
+                                       refine_iters, coord_major)
+
+
+def pose_errors(pose, P_gt) -> torch.Tensor:
+    """[RTE, RRE] of B predicted poses against B ground-truth matrices on the device (cofi_pose_errors; get_P_diff per frame,
+    evaluation/eval_all.py:16-22).  pose: a (B,12) float32 device tensor (R row-major | t) or a pair (R (B,3,3), t (B,3)); P_gt (B,4,4)
+    float64 or float32 (a host tensor / array is uploaded).  Returns a (B,2) float64 device tensor; nothing is synchronised."""
+    lib = _lib.load()
+    if isinstance(pose, (tuple, list)):
+        R, t = pose
+        if not (torch.is_tensor(R) and torch.is_tensor(t) and R.dim() == 3 and tuple(R.shape[1:]) == (3, 3) and tuple(t.shape) == (R.shape[0], 3)):
+            raise _lib.CofiError("pose_errors: (R, t) must be (B,3,3) and (B,3) tensors")
+        pose = torch.cat([R.reshape(R.shape[0], 9), t], 1)
+    if not (torch.is_tensor(pose) and pose.is_cuda and pose.dtype == torch.float32 and pose.dim() == 2 and pose.shape[1] == 12):
+        raise _lib.CofiError("pose_errors: pose must be a CUDA float32 (B,12) tensor or a pair (R (B,3,3), t (B,3))")
+    pose = pose.contiguous()
+    B = pose.shape[0]
+    if not torch.is_tensor(P_gt):
+        P_gt = torch.as_tensor(np.asarray(P_gt))
+    if tuple(P_gt.shape) != (B, 4, 4) or P_gt.dtype not in (torch.float64, torch.float32) or B == 0:
+        raise _lib.CofiError("pose_errors: P_gt must be a (B,4,4) float64 or float32 tensor with B = %d >= 1" % B)
+    P_gt = P_gt.to(pose.device, non_blocking=True).contiguous()
+    out = torch.empty((B, 2), dtype=torch.float64, device=pose.device)
+    _lib.check(lib.cofi_pose_errors(ops._p(pose), ops._p(P_gt), 1 if P_gt.dtype == torch.float64 else 0, B, ops._p(out), ops._stream()),
+               "cofi_pose_errors")
+    return out
 
 
 def euler_xzy_deg(Rm: np.ndarray) -> np.ndarray:

@@ -17,6 +17,10 @@ stack in place and several submissions are in flight.  A partly filled stack is 
 padding are dropped): every submission has the one shape its graph was captured for.  Outputs are views of the slot's static buffers:
 valid until the stack is reused, i.e. for the next `ring - 1` submissions - clone what must live longer.  Results are those of the
 stack-mode forward (per-frame statistics, frame-local gathers: `tests/test_forward_gpu.py::test_stack_mode_batch_equals_single_frames`).
+
+Frames in, poses out (`evaluation/eval_all.py:94-117` at batch rates): `FrameBatcher(model, pose=True)`, `submit(pyr, img, K)` with the
+frame's (3,3) camera matrix, and `pose_result(t)` -> (result (3,) int32 [success, inliers, hypothesis], R (3,3), t (3,), inlier mask of the
+frame's n matches): the poses of a whole stack are solved in one batched pass behind its forward (`forward_async(..., pose_K=...)`).
 """
 from typing import Dict, List, Optional, Tuple
 
@@ -27,7 +31,8 @@ from .preprocess import FrameStack
 
 
 class FrameBatcher:
-    def __init__(self, model: CoFiI2P, batch: int = 16, streams: int = 4, ring: Optional[int] = None, slot_base: int = 200):
+    def __init__(self, model: CoFiI2P, batch: int = 16, streams: int = 4, ring: Optional[int] = None, slot_base: int = 200,
+                 pose: bool = False, pose_iterations: int = 10000):
         if batch < 1:
             raise ValueError("batch must be >= 1")
         self.model, self.B = model, int(batch)
@@ -44,6 +49,11 @@ class FrameBatcher:
         self._cur, self._fill = 0, 0                                 # stack being filled, frames in it
         self._last: Optional[Tuple[Dict, torch.Tensor]] = None
         self._nsub = 0
+        self.pose, self.pose_iterations = bool(pose), int(pose_iterations)
+        self._K: List[Optional[torch.Tensor]] = [None] * self.ring   # (B,3,3) device buffer of each stack: the frames' camera matrices
+        self._poses: List[Optional[Dict]] = [None] * self.ring       # handle["pose"] of the stack's finished submission
+        self._fine: List[Optional[list]] = [None] * self.ring        # per-frame fine matches (2, n) of that submission
+        self._counts: List[Optional[List[int]]] = [None] * self.ring  # matches per frame of that submission
 
     # ------------------------------------------------------------------ internals
     def _stream(self, j: int) -> torch.cuda.Stream:
@@ -61,21 +71,40 @@ class FrameBatcher:
         try:
             res = self.model.finish(h, per_frame_errors=True)
             self._results[j] = res if isinstance(res, list) else [res]
+            self._poses[j] = h.get("pose")
+            self._fine[j] = h["fine_xy"]
+            self._counts[j] = [max(0, int(n)) for n in h["count_host"][:, 0]]
         finally:
             self._handles[j] = None
 
     def _launch(self, j: int):
         st = self._stacks[j]
         with torch.cuda.stream(self._stream(j)):
-            self._handles[j] = self.model.forward_async(self.slot_base + j, st.pyr, st.img, inputs_stable=True)
-        self._results[j] = None
+            if self.pose:
+                self._handles[j] = self.model.forward_async(self.slot_base + j, st.pyr, st.img, inputs_stable=True, pose_K=self._K[j],
+                                                            pose_iterations=self.pose_iterations)
+            else:
+                self._handles[j] = self.model.forward_async(self.slot_base + j, st.pyr, st.img, inputs_stable=True)
+        self._results[j] = self._poses[j] = self._fine[j] = self._counts[j] = None
         self._nsub += 1
 
     # ------------------------------------------------------------------ API
-    def submit(self, pc_data_dict: Dict, img: torch.Tensor) -> Tuple[int, int, int]:
+    def _put_K(self, j: int, f: int, K):
+        """the frame's camera matrix -> row f of the stack's (B,3,3) device buffer (on the current = the submission's stream)"""
+        if self._K[j] is None:
+            self._K[j] = torch.zeros((self.B, 3, 3), dtype=torch.float32, device=self._stacks[j].img.device)
+        if not torch.is_tensor(K):
+            K = torch.tensor(K, dtype=torch.float32)
+        if tuple(K.shape) != (3, 3):
+            raise ValueError("FrameBatcher.submit: K must be a (3,3) camera matrix")
+        self._K[j][f].copy_(K, non_blocking=True)
+
+    def submit(self, pc_data_dict: Dict, img: torch.Tensor, K=None) -> Tuple[int, int, int]:
         """one frame -> a ticket.  The frame's tensors are read by a copy kernel enqueued on the submission's stream before this returns
         control to the caller's NEXT enqueue on that stream only - keep them unmodified until `result()` of any later ticket, or pass
-        tensors that are not rewritten (a loader ring)."""
+        tensors that are not rewritten (a loader ring).  K: the frame's (3,3) camera matrix (host or device), required with pose=True."""
+        if self.pose and K is None:
+            raise ValueError("FrameBatcher(pose=True): submit() needs the frame's camera matrix K")
         j = self._cur
         if self._fill == 0:
             self._collect(j)                      # the stack's previous submission must have been read out before it is overwritten
@@ -94,6 +123,8 @@ class FrameBatcher:
             if self._stacks[j] is None:
                 self._stacks[j] = FrameStack(pyr, feats, img, self.B)
             self._stacks[j].put(self._fill, pyr, feats, img)
+            if self.pose:
+                self._put_K(j, self._fill, K)
         self._last = (pyr, feats, img)
         ticket = (j, self._serial[j], self._fill)
         self._fill += 1
@@ -111,6 +142,8 @@ class FrameBatcher:
         with torch.cuda.stream(self._stream(j)):
             for f in range(self._fill, self.B):
                 self._stacks[j].put(f, pyr, feats, img)
+                if self.pose:
+                    self._K[j][f].copy_(self._K[j][self._fill - 1])
         self._launch(j)
         self._cur, self._fill = (j + 1) % self.ring, 0
 
@@ -128,6 +161,28 @@ class FrameBatcher:
         if isinstance(r, Exception):
             raise r                               # this frame only: the other tickets of the stack are served
         return r
+
+    def fine_xy(self, ticket: Tuple[int, int, int]) -> torch.Tensor:
+        """-> the fine matches (2, n) of the ticket's frame (eval_all.py:99-105; `handle["fine_xy"][f]` of the stack's submission)"""
+        self.result(ticket)   # collects the submission; raises for a stale ticket or a frame without matches
+        return self._fine[ticket[0]][ticket[2]]
+
+    def pose_result(self, ticket: Tuple[int, int, int]):
+        """-> (result (3,) int32 [success, inliers, winning hypothesis], R (3,3), t (3,), inliers (n,) uint8) of the ticket's frame: device
+        views of the slot's pose buffers, same lifetime as `result(ticket)`.  A frame with fewer than 4 matches has result[0] == 0 and the
+        identity pose (its `result(ticket)` raises); its neighbours in the stack are not affected."""
+        if not self.pose:
+            raise RuntimeError("FrameBatcher: built without pose=True")
+        j, serial, f = ticket
+        if serial != self._serial[j]:
+            raise RuntimeError("FrameBatcher: the ticket's stack has been reused (results live for ring - 1 = %d later submissions)" % (self.ring - 1))
+        if j == self._cur and self._fill > 0:
+            self.flush()
+        self._collect(j)
+        if self._poses[j] is None:
+            raise RuntimeError("FrameBatcher: no submission is pending for this ticket")
+        p = self._poses[j]
+        return p["result"][f], p["R"][f], p["t"][f], p["inliers"][f, :self._counts[j][f]]
 
     @property
     def submissions(self) -> int:

@@ -585,6 +585,27 @@ size_t cofi_pnp_ransac_workspace(int iterations);
 int cofi_pnp_ransac(const float *obj, const float *img, const int32_t *count_dev, int n_max, float fx, float fy, float cx, float cy,
                     int iterations, float reproj_err, unsigned seed, int refine_iters, void *ws, size_t ws_bytes, float *pose,
                     int32_t *result, uint8_t *inlier_mask, cofi_stream_t stream);
+/* The same solver for `frames` frames of a stack-mode submission in two launches (hypotheses + consensus with the frame on the grid's
+ * second axis, one refit workgroup per frame).  Frame f is bit-identical to cofi_pnp_ransac on that frame's operands with seed + f: both
+ * forms run the same device functions.  Operands are addressed in place, as the stack-mode forward leaves them:
+ *   obj    frame f at obj + f * obj_frame_stride floats, (n_max, 3)
+ *   img    frame f at img + f * img_frame_stride floats; point-major (n_max, 2), or coordinate-major (2, n_max) if coord_major != 0
+ *          (the fine_xy of cofi_match_finish)
+ *   count_dev[f * count_stride] = valid rows of frame f (NULL: n_max for every frame); fewer than 4: result {0, 0, -1}, identity pose
+ *   K_dev  (frames, 3, 3) float32 row-major in DEVICE memory: fx, fy, cx, cy are read by the kernels (no host copy of the intrinsics);
+ *          a frame whose fx or fy is not positive reports failure
+ * Outputs: pose (frames, 12), result (frames, 3), inlier_mask (frames, n_max).  Workspace: one key per frame + iterations x 12 floats
+ * per frame.  The hypotheses kernel stages a frame's correspondences in LDS (20 bytes each) when n_max <= 3276, and reads global
+ * memory beyond. */
+size_t cofi_pnp_ransac_batch_workspace(int iterations, int frames);
+int cofi_pnp_ransac_batch(const float *obj, int obj_frame_stride, const float *img, int img_frame_stride, int coord_major,
+                          const int32_t *count_dev, int count_stride, const float *K_dev, int n_max, int frames, int iterations,
+                          float reproj_err, unsigned seed, int refine_iters, void *ws, size_t ws_bytes, float *pose, int32_t *result,
+                          uint8_t *inlier_mask, cofi_stream_t stream);
+/* The registration errors of evaluation/eval_all.py:16-22 for `frames` poses: P_diff = inv(P_pred) P_gt (general fp64 inverse),
+ * out (frames, 2) float64 = [RTE = |t(P_diff)|, RRE = sum |euler 'xzy' of R(P_diff)| in degrees, scipy's gimbal convention].
+ * pose (frames, 12) as cofi_pnp_ransac writes it; P_gt (frames, 4, 4) row-major, float64 if gt_is_f64 != 0, else float32. */
+int cofi_pose_errors(const float *pose, const void *P_gt, int gt_is_f64, int frames, double *out, cofi_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Row f2: the data side of one frame on the device, replacing the numpy / open3d / cv2 part of
