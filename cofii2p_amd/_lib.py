@@ -135,6 +135,10 @@ SIGNATURES = {
     "cofi_pnp_ransac_batch_workspace": (_Z, [_I, _I]),
     "cofi_pnp_ransac_batch": (_I, [_P, _I, _P, _I, _I, _P, _I, _P, _I, _I, _I, _F, ctypes.c_uint, _I, _P, _Z, _P, _P, _P, _P]),
     "cofi_pose_errors": (_I, [_P, _P, _I, _I, _P, _P]),
+    "cofi_val_gather": (_I, [_P, _I, _I, _I, _I, _P, _I, _I, _P, _P, _I, _I, _I, _P, _P, _P]),
+    "cofi_val_monitors_workspace": (_Z, [_I, _I]),
+    "cofi_val_monitors": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _I, _P, _P, _F, _I, _I, _I, _P, _P, _P, _P, _P, _P,
+                               _P, _Z, _P]),
     "cofi_match_finish": (_I, [_P, _P, _I, _P, _P, _I, _P, _I, _I, _I, _I, _P, _I, _F, _P, _I, _P, _P, _P, _I, _P, _P, _I, _I, _P]),
     "cofi_fine_match": (_I, [_P, _P, _I, _I, _P, _I, _F, _P, _I, _P, _P, _P]),
     "cofi_kpconv_fused_slab_rows": (_I, [_I, _I, _I]),

@@ -219,8 +219,13 @@ class CoFiI2P(nn.Module):
         with one entry per frame."""
         dev = img.device
         B = img.shape[0]
-        if mode != "test" and B != 1:
-            raise ValueError("stack mode (B > 1) serves mode='test'")
+        if mode not in ("test", "val") and B != 1:
+            raise ValueError("stack mode (B > 1) serves mode='test' and mode='val'")
+        # mode='val' with labels of a whole submission - fine_center_kpt_coors (B, 2, K), fine_pc_inline_index (B, K), int64 / int32 device
+        # tensors - takes the batched label gathers (forward_val_async); the (2, K) / (K,) labels of forward() keep the single-frame launches
+        val_batched = mode == "val" and fine_center_kpt_coors is not None and fine_center_kpt_coors.dim() == 3
+        if B != 1 and mode == "val" and not val_batched:
+            raise ValueError("stack mode (B > 1) in mode='val' needs labels of shape (B, 2, K) / (B, K): forward_val_async")
         N4 = points[-1].shape[0] // B
         H8, W8 = img.shape[2] // 8, img.shape[3] // 8
         T_img, C = H8 * W8, D_MODEL
@@ -304,13 +309,20 @@ class CoFiI2P(nn.Module):
             if C2 <= 128:   # coarse point, point2node, patch, fine descriptor and the caller's fine matching (eval_all.py:99-105): one launch
                 cpts, pat, fpcs, fxy, fbest = (t if B > 1 else t[None] for t in
                                                ops.match_finish(points[-1], points[1], sel, cnt, up2, H2, W2, xy, fine_pc, 4.0, frames=B))
+        if val_batched:   # network.py:137-141 for all frames: one launch (cofi_val_gather), labels read in place
+            K = fine_center_kpt_coors.shape[2]
+            if tuple(fine_center_kpt_coors.shape) != (B, 2, K) or tuple(fine_pc_inline_index.shape) != (B, K):
+                raise _lib.CofiError("mode='val' stack labels: fine_center_kpt_coors (B, 2, K) and fine_pc_inline_index (B, K) with B = %d" % B)
+            pat_all, fpc_all = ops.val_gather(up2, H2, W2, fine_pc, fine_center_kpt_coors, fine_pc_inline_index)
         outs = []
         for f in range(B):  # per-frame views
             o = {"img_desc": img_t[f].reshape(1, C, H8, W8), "pc_desc": pc_t[f],
                  "img_score": img_score[f * T_img:(f + 1) * T_img].reshape(1, 1, H8, W8), "pc_score": pc_score[f * N4:(f + 1) * N4].reshape(1, 1, N4)}
             fpc = fine_pc[f * N1:(f + 1) * N1]
             up2_f = up2[f * P2:(f + 1) * P2]
-            if not test:
+            if val_batched:
+                o["patches"], o["fine_pc"] = pat_all[f].reshape(K, C2, 4, 4), fpc_all[f]
+            elif not test:
                 K = fine_center_kpt_coors.shape[1]
                 cntk = torch.zeros((2,), dtype=torch.int32, device=dev)
                 cntk[:1].fill_(K)   # a fill kernel, not a host-to-device copy: capturable in a hipGraph
@@ -334,6 +346,9 @@ class CoFiI2P(nn.Module):
             outs[0]["count_all"] = cnt   # (B, 2): one device-to-host copy serves every frame of the submission
             if C2 <= 128:   # what a batched consumer of the matches reads in place (pose.solve_pnp_ransac_batch): (B, cap, 3), (B, 2, cap)
                 outs[0]["coarse_pts_all"], outs[0]["fine_xy_all"] = cpts, fxy
+        if val_batched:   # what the batched consumer (validation.val_monitors) reads in place, and the maps the gathers came from
+            outs[0].update(patches_all=pat_all, fine_pc_all=fpc_all, img_desc_all=img_t, pc_desc_all=pc_t, pc_score_all=pc_score,
+                           points4=points[-1], fine_img_map=up2, fine_pc_map=fine_pc)
         br_dead.join()
         return outs
 
@@ -540,6 +555,57 @@ class CoFiI2P(nn.Module):
         if pose is not None:
             handle["pose"] = pose
         return handle
+
+    @torch.no_grad()
+    def forward_val_async(self, slot: int, pc_data_dict, img, fine_center_kpt_coors, fine_pc_inline_index, inputs_stable: bool = False):
+        """The validation pass's forward (train.py:68-70: model.eval(), mode='val') for B frames as ONE stack-mode submission on the
+        current stream, through the hipGraph of slot `slot` (per slot and input signature; the labels are part of the staged inputs).
+        `img` (B,3,H,W) with a stack-mode `pc_data_dict` (see stack_frames); fine_center_kpt_coors (B, 2, K) and fine_pc_inline_index
+        (B, K): int64 or int32 DEVICE tensors, frame-local, read by the gather kernel without a host copy.  Returns at once with a handle:
+        handle["out"][f] holds frame f's views (img_desc, pc_desc, img_score, pc_score, patches (K, C2, 4, 4), fine_pc (K, C2)),
+        handle["out"][0] also the submission-wide tensors validation.val_monitors reads in place (patches_all (B, K, C2, 16), fine_pc_all
+        (B, K, C2), ...); `finish_val(handle)` synchronises on this submission and returns the reference's tuples.  Slots, their reuse and
+        inputs_stable are those of forward_async.  Inference only: a module in train() mode is refused (batch statistics belong to
+        forward(mode='val') there), and mode='train' keeps refusing B > 1."""
+        if self.training:
+            raise ValueError("forward_val_async is the eval()-mode validation pass (train.py:37): call model.eval() first")
+        _lib.load()
+        labels = []
+        for name, t, shape in (("fine_center_kpt_coors", fine_center_kpt_coors, (img.shape[0], 2)), ("fine_pc_inline_index", fine_pc_inline_index, (img.shape[0],))):
+            if not torch.is_tensor(t) or not t.is_cuda or t.dim() != len(shape) + 1 or tuple(t.shape[:-1]) != shape:
+                raise _lib.CofiError("forward_val_async: %s must be a device tensor of shape %s + (K,)" % (name, shape))
+            if t.dtype not in (torch.int64, torch.int32):
+                raise _lib.CofiError("forward_val_async: %s must be int64 or int32, got %s" % (name, t.dtype))
+            if inputs_stable and not t.is_contiguous():
+                raise _lib.CofiError("inputs_stable=True reads the labels in place: contiguous int64 / int32 tensors only (%s)" % name)
+            labels.append(t.contiguous())
+        if labels[0].dtype != labels[1].dtype:
+            if inputs_stable:
+                raise _lib.CofiError("inputs_stable=True reads the labels in place: one integer dtype for both")
+            labels = [t.to(torch.int64) for t in labels]
+        if inputs_stable:   # as forward_async: the graph reads these very tensors
+            for k in ("points", "neighbors", "subsampling", "upsampling"):
+                for t in pc_data_dict[k]:
+                    if not t.is_contiguous() or (k != "points" and t.dtype != torch.int32):
+                        raise _lib.CofiError("inputs_stable=True reads the inputs in place: contiguous tensors and int32 tables only (%s)" % k)
+            if not (pc_data_dict["feats"].is_contiguous() and img.is_contiguous()):
+                raise _lib.CofiError("inputs_stable=True reads the inputs in place: contiguous feats / img only")
+        with ops.arithmetic(self.arithmetic):
+            P = self._pack(img.device)
+            points = [p.contiguous() for p in pc_data_dict["points"]]
+            tabs = [[self._as_idx32(t) for t in pc_data_dict[k]] for k in ("neighbors", "subsampling", "upsampling")]
+            outs = self._graph_forward(P, points, tabs[0], tabs[1], tabs[2], pc_data_dict["feats"].contiguous(), img.contiguous(), "val",
+                                       labels[0], labels[1], slot=slot, branch_mask=self.async_branch_mask,
+                                       order=pc_data_dict.get("order"), inputs_stable=inputs_stable)
+        done = torch.cuda.Event()
+        done.record()
+        return {"out": outs, "done": done, "mode": "val"}
+
+    def finish_val(self, handle):
+        """-> the reference's 8-tuple (mode='val': the last two entries are None) for every frame of a forward_val_async submission.
+        The tensors are views of the slot's static outputs, valid until the slot is reused."""
+        handle["done"].synchronize()
+        return [(o["img_desc"], o["pc_desc"], o["img_score"], o["pc_score"], o["patches"], o["fine_pc"], None, None) for o in handle["out"]]
 
     def _slice_result(self, o, n: int, thr_i: int):
         if thr_i < 0:

@@ -1267,3 +1267,72 @@ def match_finish(pts4, pts1, sel, cnt, fmap, H2: int, W2: int, xy, fine_pc_all, 
                                C, _p(fine_xy), _p(best), pts4.shape[0] // frames, frames, _stream())
     _lib.check(rc, "cofi_match_finish")
     return coarse_pts, patches, fine_pc, fine_xy, best
+
+
+# ------------------------------------------------------------------------------------------ validation pass (csrc/validation.hip)
+def _label(t: torch.Tensor, name: str, shape, dtype) -> torch.Tensor:
+    if not t.is_cuda or t.dtype != dtype or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
+        raise _lib.CofiError("%s: expected a contiguous CUDA %s of shape %s, got %s %s" % (name, dtype, tuple(shape), t.dtype, tuple(t.shape)))
+    return t
+
+
+def val_gather(fmap, H2: int, W2: int, fine_pc_map, centers, inline_idx):
+    """The label gathers of a val-mode forward (network.py:137-141) for all frames in one launch: fmap (B*H2*W2, C) pixel-major fine image
+    maps, fine_pc_map (B*N1, C), centers (B, 2, K) and inline_idx (B, K) int64 or int32 device tensors (frame-local, read in place)
+    -> patches (B, K, C, 16), fine_pc (B, K, C)."""
+    lib = _lib.load()
+    _mat(fmap, "fmap"), _mat(fine_pc_map, "fine_pc_map")
+    if centers.dim() != 3 or centers.shape[1] != 2 or centers.dtype not in (torch.int64, torch.int32):
+        raise _lib.CofiError("val_gather: centers must be (B, 2, K) int64 or int32")
+    B, _, K = centers.shape
+    _label(centers, "centers", (B, 2, K), centers.dtype), _label(inline_idx, "inline_idx", (B, K), centers.dtype)
+    C = fmap.shape[1]
+    if fmap.shape[0] != B * H2 * W2 or fine_pc_map.shape[0] % B or fine_pc_map.shape[1] != C:
+        raise _lib.CofiError("val_gather: shape mismatch")
+    patches = torch.empty((B, K, C, 16), dtype=torch.float32, device=fmap.device)
+    fine_pc = torch.empty((B, K, C), dtype=torch.float32, device=fmap.device)
+    rc = lib.cofi_val_gather(_p(fmap), _ld(fmap), C, H2, W2, _p(fine_pc_map), _ld(fine_pc_map), fine_pc_map.shape[0] // B, _p(centers),
+                             _p(inline_idx), int(centers.dtype == torch.int64), K, B, _p(patches), _p(fine_pc), _stream())
+    _lib.check(rc, "cofi_val_gather")
+    return patches, fine_pc
+
+
+def val_monitors(img_desc, pc_desc, W8: int, points4, pc_score, patches, fine_pc, labels, K_4, P, dist_thres: float, topk: int = 5,
+                 debug: bool = False, out=None):
+    """cofi_val_monitors on B frames: img_desc (B, C, T), pc_desc (B, C, N4) channel-major, points4 (B*N4, 3), pc_score (B*N4 values),
+    patches (B, K, C2, 16), fine_pc (B, K, C2); labels: dict of pc_kpt_idx / pc_outline_idx / coarse_img_kpt_idx (B, K) and fine_xy /
+    fine_center_kpt_coors (B, 2, K), one integer dtype (int64 or int32); K_4 (B, 3, 3), P (B, 4, 4) float32.
+    -> dict counts (B, topk) int32, n_true (B,), fine_hits (B,), score_stats (B, 6) float32 (+ dist, mask (B, K, K) with debug=True).
+    `out`: a dict of such tensors to write into (a recording keeps its addresses)."""
+    lib = _lib.load()
+    B, C, T = img_desc.shape
+    N4 = pc_desc.shape[2]
+    dt = labels["pc_kpt_idx"].dtype
+    if dt not in (torch.int64, torch.int32):
+        raise _lib.CofiError("val_monitors: labels must be int64 or int32")
+    K = labels["pc_kpt_idx"].shape[1]
+    for k in ("pc_kpt_idx", "pc_outline_idx", "coarse_img_kpt_idx"):
+        _label(labels[k], k, (B, K), dt)
+    for k in ("fine_xy", "fine_center_kpt_coors"):
+        _label(labels[k], k, (B, 2, K), dt)
+    _label(K_4, "K_4", (B, 3, 3), torch.float32), _label(P, "P", (B, 4, 4), torch.float32)
+    C2 = fine_pc.shape[2]
+    _label(img_desc, "img_desc", (B, C, T), torch.float32), _label(pc_desc, "pc_desc", (B, C, N4), torch.float32)
+    _label(points4, "points4", (B * N4, 3), torch.float32)
+    _label(patches, "patches", (B, K, C2, 16), torch.float32), _label(fine_pc, "fine_pc", (B, K, C2), torch.float32)
+    if not pc_score.is_cuda or pc_score.dtype != torch.float32 or pc_score.numel() != B * N4 or not pc_score.is_contiguous():
+        raise _lib.CofiError("val_monitors: pc_score must hold B * N4 contiguous float32 values")
+    dev = img_desc.device
+    o = {} if out is None else out
+    for name, shape, dtype in (("counts", (B, topk), torch.int32), ("n_true", (B,), torch.int32), ("fine_hits", (B,), torch.int32),
+                               ("score_stats", (B, 6), torch.float32)) + ((("dist", (B, K, K), torch.float32), ("mask", (B, K, K), torch.float32)) if debug else ()):
+        if name not in o:
+            o[name] = torch.empty(shape, dtype=dtype, device=dev)
+        _label(o[name], name, shape, dtype)
+    rc = lib.cofi_val_monitors(_p(img_desc), _p(pc_desc), C, T, W8, N4, _p(points4), _p(pc_score), _p(patches), _p(fine_pc), C2,
+                               _p(labels["pc_kpt_idx"]), _p(labels["pc_outline_idx"]), _p(labels["coarse_img_kpt_idx"]), _p(labels["fine_xy"]),
+                               _p(labels["fine_center_kpt_coors"]), int(dt == torch.int64), _p(K_4), _p(P), float(dist_thres), K, B, int(topk),
+                               _p(o["counts"]), _p(o["n_true"]), _p(o["fine_hits"]), _p(o["score_stats"]), _p(o.get("dist")), _p(o.get("mask")),
+                               None, 0, _stream())
+    _lib.check(rc, "cofi_val_monitors")
+    return o

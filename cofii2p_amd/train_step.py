@@ -98,9 +98,12 @@ class GraphedTrainStep:
     * Do not keep the outputs / loss tensors of an EAGER step of the same module alive across the recording call: their autograd
       graph pins gradient-accumulation nodes to the eager stream, which breaks a capture (torch warns, HIP aborts).
     * After replays the module's packed inference weights are refreshed on the next inference forward, as after eager steps.
+    * `monitors=True` appends `validation.train_monitors` (train.py:256-259 and :268-280 on the device: one launch reading the step's
+      forward outputs) to the step and to its recording; `step.monitors` then holds THAT step's counts / n_true / fine_hits / score_stats
+      as device tensors.  With the default nothing about the step, its recording or its return value changes.
     """
 
-    def __init__(self, model, optimizer, opt, validate: bool = True):
+    def __init__(self, model, optimizer, opt, validate: bool = True, monitors: bool = False):
         for g in optimizer.param_groups:
             if not g.get("capturable", False):
                 raise ValueError("GraphedTrainStep needs a capturable optimizer (torch.optim.Adam(..., capturable=True)): a host-side "
@@ -113,6 +116,14 @@ class GraphedTrainStep:
         self._losses: Optional[torch.Tensor] = None
         self._lr: List[torch.Tensor] = []
         self.replays = 0
+        self.with_monitors = bool(monitors)
+        self.monitors: Optional[Dict[str, torch.Tensor]] = None
+        self._monitors: Optional[Dict[str, torch.Tensor]] = None
+
+    def _run_monitors(self, outs, spc, sbatch):
+        from . import validation
+
+        return validation.train_monitors(outs, spc, sbatch, self.opt)
 
     def _capture_stream(self, dev) -> torch.cuda.Stream:
         if getattr(self, "_cap", None) is None or self._cap.device != torch.device(dev):
@@ -188,6 +199,8 @@ class GraphedTrainStep:
             (l_desc + l_coarse + l_fine).backward()
             self.optimizer.step()
             self._losses = torch.stack([l_desc.detach(), l_coarse.detach(), l_fine.detach()])
+            if self.with_monitors:
+                self._monitors = self._run_monitors(_o, spc, sbatch)
         self._graph = graph
 
     def __call__(self, pc_data_dict, img, batch) -> torch.Tensor:
@@ -214,8 +227,13 @@ class GraphedTrainStep:
                 (l_desc + l_coarse + l_fine).backward()
                 self.optimizer.step()
                 out = torch.stack([l_desc.detach(), l_coarse.detach(), l_fine.detach()])
+                if self.with_monitors:
+                    self.monitors = self._run_monitors(_o, spc, sbatch)
             cur.wait_stream(cap)
             out.record_stream(cur)
+            if self.with_monitors:
+                for t in self.monitors.values():
+                    t.record_stream(cur)
             return out
         if self._graph is None:
             self._record()
@@ -224,4 +242,6 @@ class GraphedTrainStep:
         for m in self.model.modules():      # parameters changed behind their version counters: CoFiI2P._pack() looks at this count
             if hasattr(m, "_replayed_steps"):
                 m._replayed_steps += 1
+        if self.with_monitors:
+            self.monitors = {k: v.clone() for k, v in self._monitors.items()}
         return self._losses.clone()

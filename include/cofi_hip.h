@@ -608,6 +608,44 @@ int cofi_pnp_ransac_batch(const float *obj, int obj_frame_stride, const float *i
 int cofi_pose_errors(const float *pose, const void *P_gt, int gt_is_f64, int frames, double *out, cofi_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * The validation pass of train.py (test_acc, train.py:27-106; fine_recall, :271-281; the pc_score scalars, :256-259) for the `frames`
+ * frames of a stack-mode mode='val' submission, with no host read.  Label tensors are device tensors, all int64 (idx_is_i64 != 0) or all
+ * int32, laid out (frames, K) - index lists, frame-local - or (frames, 2, K) - pixel coordinates, x row first.
+ *
+ * cofi_val_gather: the label gathers of network.py:137-141 for every frame in one launch.
+ *   patches (frames, K, C, 16) = extract_patch(fmap of frame f (H2*W2, C) pixel-major, centers[f]) (network.py:206-226; zero outside the map),
+ *   fine_pc (frames, K, C)     = row inline_idx[f, k] of frame f's fine point descriptors fine_pc_map (frames * N1, ldfpc) (zero row for an
+ *   index outside [0, N1)).
+ *
+ * cofi_val_monitors: per frame f, reading the forward's outputs in place - img_desc (frames, C, T) and pc_desc (frames, C, N4)
+ * channel-major coarse descriptors (T = H8 * W8 pixels of a W8 wide map), points4 (frames * N4, 3), pc_score (frames * N4),
+ * patches / fine_pc as cofi_val_gather writes them, K_4 (frames, 3, 3), P (frames, 4, 4) -
+ *   img_i / pc_j   = the descriptor columns coarse_img_kpt_idx[f, i] / pc_kpt_idx[f, j]                              (train.py:72-78)
+ *   pc_xy_j        = proj[:2] / proj[2], proj = K_4 (P[:3,:3] x_j + P[:3,3])                                          (train.py:80-82)
+ *   mask[i, j]     = sqrt(|img_xy_i - pc_xy_j|^2) <= dist_thres, img_xy = (index % W8, index / W8)                    (train.py:84)
+ *   dist[i, j]     = 1 - <img_i, pc_j>, one fp32 fmaf chain over the channels in ascending order                       (train.py:86)
+ *   n_true[f]      = the number of entries with mask set and dist != 0: the reference's true_value_list                (train.py:89-91)
+ *   counts[f, k-1] = over all rows, how many of the row's k smallest dist values (ascending, torch.sort) EQUAL ANY VALUE of the
+ *                    true list - membership by value over the whole matrix, not by position, as `candidate in true_value_list`
+ *                    (train.py:92-101); counts (frames, topk), topk <= 8 and <= K
+ *   fine_hits[f]   = key points whose arg-max over the 16 patch pixels of the cosine similarity with fine_pc (cofi_fine_match's
+ *                    arithmetic and first-index tie rule) equals (fine_xy - fine_center_kpt_coors + 2) folded as y * 4 + x  (train.py:268-279)
+ *   score_stats[f] = [max, min, mean] of pc_score at pc_kpt_idx[f], then at pc_outline_idx[f]                            (train.py:256-259)
+ * dist_out / mask_out (frames, K, K) fp32, optional (NULL to skip): the distance matrix and the mask (1 / 0) the counts come from.
+ * One launch: workgroup (f, 0) holds the distance tile and the true-value list in LDS, workgroup (f, 1) the fine and score part.
+ * K <= 128 and C <= 128 (what fits the LDS of one workgroup); COFI_EUNSUPPORTED beyond.  Label indices outside their table are clamped
+ * into it.  The workspace is empty (the query returns 0); ws may be NULL. */
+int cofi_val_gather(const float *fmap, int ldf, int C, int H2, int W2, const float *fine_pc_map, int ldfpc, int N1, const void *centers,
+                    const void *inline_idx, int idx_is_i64, int K, int frames, float *patches, float *fine_pc, cofi_stream_t stream);
+size_t cofi_val_monitors_workspace(int K, int frames);
+int cofi_val_monitors(const float *img_desc, const float *pc_desc, int C, int T, int W8, int N4, const float *points4,
+                      const float *pc_score, const float *patches, const float *fine_pc, int C2, const void *pc_kpt_idx,
+                      const void *pc_outline_idx, const void *coarse_img_kpt_idx, const void *fine_xy, const void *fine_center_kpt_coors,
+                      int idx_is_i64, const float *K_4, const float *P, float dist_thres, int K, int frames, int topk, int32_t *counts,
+                      int32_t *n_true, int32_t *fine_hits, float *score_stats, float *dist_out, float *mask_out, void *ws,
+                      size_t ws_bytes, cofi_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Row f2: the data side of one frame on the device, replacing the numpy / open3d / cv2 part of
  *   kitti_pc_img_dataset.__getitem__                                        (data/kitti.py:259-393)
  * between the disk read and the model call.  The random draws (choice indices, SE(3), permutations) are made on the host in the
