@@ -229,7 +229,8 @@ extern "C" int cofi_fine_circle_loss(const float *patches, const float *pc, int 
 
 extern "C" int cofi_overlap_loss(const float *inline_score, int n_in, const float *outline_score, int n_out, float *loss, const float *grad_out,
                                  float *grad_in, float *grad_outline, cofi_stream_t stream) {
-    if (!inline_score || !outline_score || n_in < 0 || n_out < 0 || n_in + n_out <= 0 || (!loss && !grad_out)) return COFI_EINVAL;
+    if (n_in < 0 || n_out < 0 || n_in + n_out <= 0 || (!loss && !grad_out)) return COFI_EINVAL;
+    if ((n_in > 0 && !inline_score) || (n_out > 0 && !outline_score)) return COFI_EINVAL;   // an empty side may be NULL (torch's empty tensors are)
     hipLaunchKernelGGL(bce_kernel, dim3(1), dim3(64), 0, cofi_s(stream), inline_score, n_in, outline_score, n_out, loss, grad_out, grad_in,
                        grad_outline);
     return cofi_launch_status();
