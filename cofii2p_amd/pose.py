@@ -82,6 +82,28 @@ def pnp_batch_workspace(iterations: int, frames: int) -> int:
     return _lib.load().cofi_pnp_ransac_batch_workspace(int(iterations), int(frames))
 
 
+def pnp_batch_workspace_views(ws: torch.Tensor, iterations: int, frames: int):
+    """(keys, poses): views of a workspace of solve_pnp_ransac_batch_into in the layout cofi_pnp_ransac_batch documents - one consensus
+    key per frame (padded to 64 bytes), then one slab of iterations x 12 floats per frame.  keys (frames,) int64, decoded by
+    pnp_decode_key; poses (frames, iterations, 12) float32: row h of a frame is hypothesis h (R row-major | t), written only if that
+    hypothesis produced a pose.  For tests and tools: the product never looks inside the workspace."""
+    iterations, frames = int(iterations), int(frames)
+    need = pnp_batch_workspace(iterations, frames)
+    slab_bytes = frames * iterations * 12 * 4
+    if not (torch.is_tensor(ws) and ws.dtype == torch.uint8 and ws.dim() == 1 and ws.is_contiguous() and need > 0 and ws.numel() >= need):
+        raise _lib.CofiError("pnp_batch_workspace_views: ws must be a contiguous uint8 tensor of at least pnp_batch_workspace(%d, %d) = %d bytes"
+                             % (iterations, frames, need))
+    key_bytes = need - slab_bytes   # the padded key block: the size is the library's own
+    return ws[:8 * frames].view(torch.int64), ws[key_bytes:need].view(torch.float32).view(frames, iterations, 12)
+
+
+def pnp_decode_key(key):
+    """(inliers, hypothesis) of a consensus key (inliers << 32 | 0xFFFFFFFF - hypothesis: most inliers win, lowest id on ties).
+    A key of 0 - no hypothesis of the frame produced a pose - decodes to (0, 0xFFFFFFFF)."""
+    key = int(key)
+    return key >> 32, 0xFFFFFFFF - (key & 0xFFFFFFFF)
+
+
 def solve_pnp_ransac_batch_into(object_points, image_points, K, count, ws, pose, result, mask, iterations: int = 10000,
                                 reproj_error: float = 8.0, seed: int = 0, refine_iters: int = 20, coord_major: bool = False):
     """solve_pnp_ransac_batch into caller-owned buffers (ws uint8, pose (B,12) float32, result (B,3) int32, mask (B,cap) uint8): the
