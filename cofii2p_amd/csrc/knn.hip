@@ -16,7 +16,7 @@
 // a full buffer is bitonic-sorted across the wave and bitonic-merged into the list.  After the first
 // few hundred candidates almost nothing passes the threshold, so the stream runs at ~10 VALU
 // instructions per 64 distances.
-#include "knn_common.h"
+#include "match_parts.h"
 
 namespace {
 
@@ -84,7 +84,7 @@ __global__ __launch_bounds__(1024) void knn_topk_kernel(const float *support, in
     best.emit(q, k, S, lane, out_idx, out_dist);
 }
 
-// k = 1: nearest support row per query, lowest index on ties.  One wave per query; if sel != NULL
+// k = 1: nearest support row per query, lowest index on ties (nearest_scan, match_parts.h).  One wave per query; if sel != NULL
 // the query rows are points[sel[i]] and the row count is read from count_dev on the device.
 __global__ __launch_bounds__(256) void nearest_kernel(const float *nodes, int S, const float *points, const int32_t *sel,
                                                       const int32_t *count_dev, int Q, int32_t *out_idx) {
@@ -94,35 +94,7 @@ __global__ __launch_bounds__(256) void nearest_kernel(const float *nodes, int S,
     if (q >= nq) return;
     const size_t row = sel ? (size_t)sel[q] : (size_t)q;
     const float qx = points[3 * row], qy = points[3 * row + 1], qz = points[3 * row + 2];
-    const float qq = canon_sqnorm(qx, qy, qz);
-    u64 best = KEY_INF;
-    // 4 candidates per lane and round, all 12 loads issued before the first distance: the scan is bound by the L2 round trip
-    // per round, not by arithmetic.  The (distance, index) key makes the result independent of the visiting order.
-    for (int c0 = lane; c0 < S; c0 += 256) {
-        float px[4], py[4], pz[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const int c = min(c0 + 64 * u, S - 1);
-            px[u] = nodes[3 * (size_t)c];
-            py[u] = nodes[3 * (size_t)c + 1];
-            pz[u] = nodes[3 * (size_t)c + 2];
-        }
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const int c = c0 + 64 * u;
-            float4 sp;
-            sp.x = px[u]; sp.y = py[u]; sp.z = pz[u];
-            sp.w = canon_sqnorm(sp.x, sp.y, sp.z);
-            const float d = canon_dist(qx, qy, qz, qq, sp.x, sp.y, sp.z, sp.w);
-            if (c < S) best = umin64(best, ((u64)__float_as_uint(d) << 32) | (unsigned)c);
-        }
-    }
-    best = umin64(best, lane_xor64<32>(best, lane));
-    best = umin64(best, lane_xor64<16>(best, lane));
-    best = umin64(best, lane_xor64<8>(best, lane));
-    best = umin64(best, lane_xor64<4>(best, lane));
-    best = umin64(best, lane_xor64<2>(best, lane));
-    best = umin64(best, lane_xor64<1>(best, lane));
+    const u64 best = wave_min_key(nearest_scan<64>(nodes, S, qx, qy, qz, lane));
     if (lane == 0) out_idx[q] = (int)(unsigned)(best & 0xffffffffu);
 }
 

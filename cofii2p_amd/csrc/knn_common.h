@@ -60,6 +60,15 @@ template <int J>
 __device__ __forceinline__ u64 lane_xor64(u64 v, int) {
     return ((u64)lane_xor32<J>((unsigned)(v >> 32)) << 32) | lane_xor32<J>((unsigned)v);
 }
+// smallest key of the wave, in every lane (a minimum of integers: the exchange order cannot change the result)
+__device__ __forceinline__ u64 wave_min_key(u64 k) {
+    k = umin64(k, lane_xor64<32>(k, 0));
+    k = umin64(k, lane_xor64<16>(k, 0));
+    k = umin64(k, lane_xor64<8>(k, 0));
+    k = umin64(k, lane_xor64<4>(k, 0));
+    k = umin64(k, lane_xor64<2>(k, 0));
+    return umin64(k, lane_xor64<1>(k, 0));
+}
 // value of lane (63 - lane): in-row mirror, then swap the rows pairwise and the halves
 __device__ __forceinline__ unsigned lane_rev32(unsigned v) { return lane_xor32<32>(lane_xor32<16>(dpp_mov<0x140>(v))); }
 __device__ __forceinline__ u64 lane_rev64(u64 v, int) { return ((u64)lane_rev32((unsigned)(v >> 32)) << 32) | lane_rev32((unsigned)v); }

@@ -5,7 +5,7 @@
 // Sizes are tiny (num_kpt = 64 / 32 key points, 128 / 64 channels): latency-bound, one small launch per step, no MFMA.  Every reduction
 // has a fixed order (wave butterflies, ascending strides): bit-reproducible.  The weights the reference detaches (pos_weight,
 // neg_weight, ap, an) are treated as constants in the gradients, exactly as autograd does.
-#include "common.h"
+#include "match_parts.h"
 
 namespace {
 
@@ -108,7 +108,7 @@ __global__ void desc_grad_feats_kernel(DescArgs a, const float *G, float *gimg, 
 }
 
 // ---------------------------------------------------------------------------------------- fine_circle_loss
-// one wave per key point: lane = (pixel p = lane & 15, channel quarter = lane >> 4), as cofi_fine_match
+// one wave per key point: lane = (pixel p = lane & 15, channel quarter = lane >> 4); the cosine is cofi_fine_match's (fine_cosine16)
 struct CircleArgs {
     const float *patches;   // (K, C, 16)
     const float *pc;        // (K, C) rows of ldp
@@ -122,18 +122,9 @@ struct CircleArgs {
 
 __global__ __launch_bounds__(64) void circle_kernel(CircleArgs a) {
     const int k = blockIdx.x, lane = threadIdx.x, p = lane & 15, part = lane >> 4;
-    float dot = 0.f, nn = 0.f, pp = 0.f;
-    for (int c = part; c < a.C; c += 4) {
-        const float pv = a.patches[((size_t)k * a.C + c) * 16 + p], fv = a.pc[(size_t)k * a.ldp + c];
-        dot += pv * fv;
-        nn += pv * pv;
-        pp += fv * fv;
-    }
-    dot += __shfl_xor(dot, 16, 64); dot += __shfl_xor(dot, 32, 64);
-    nn += __shfl_xor(nn, 16, 64);   nn += __shfl_xor(nn, 32, 64);
-    pp += __shfl_xor(pp, 16, 64);   pp += __shfl_xor(pp, 32, 64);
-    const float nx = fmaxf(sqrtf(nn), 1e-8f), ny = fmaxf(sqrtf(pp), 1e-8f);
-    const float dist = dot / (nx * ny);                       // torch.cosine_similarity, eps 1e-8
+    const Cosine16 cs = fine_cosine16([&](int c, int pxl) { return a.patches[((size_t)k * a.C + c) * 16 + pxl]; },
+                                      [&](int c) { return a.pc[(size_t)k * a.ldp + c]; }, a.C, lane);
+    const float nx = cs.nx, ny = cs.ny, dist = cs.sim();
     const float pos = (p == (int)a.rel[k]) ? 1.f : 0.f, neg = 1.f - pos;
     const float sp = dist * pos, sn = dist * neg;
     const float ap = fmaxf(-sp + pos + pos * a.m, 0.f), an = fmaxf(sn + neg * a.m, 0.f);   // detached in the reference

@@ -3,8 +3,7 @@
 // (`extract_patch`), evaluation/eval_all.py:99-105 (fine matching in the caller).
 // The match count stays on the device (count_dev); downstream kernels are launched at capacity and
 // read it, so the only host synchronisation of a test-mode forward is the final read of the count.
-#include "common.h"
-#include "knn_common.h"
+#include "match_parts.h"
 
 namespace {
 
@@ -88,21 +87,11 @@ __global__ __launch_bounds__(SEL_NT) void select_matches_kernel(SelArgs a) {
             x = p % a.W8; y = p / a.W8;
             ok = a.score[n] >= thr && x >= 2 && x <= a.xmax && y >= 2 && y <= a.ymax;
         }
-        const unsigned long long m = __ballot(ok);
-        if (lane == 0) s_cnt[wave] = __popcll(m);
-        __syncthreads();
-        int off = base;
-        for (int w = 0; w < wave; ++w) off += s_cnt[w];
-        int tot = 0;
-        for (int w = 0; w < SEL_NW; ++w) tot += s_cnt[w];
-        if (ok) {
-            const int pos = off + __popcll(m & ((1ull << lane) - 1ull));
+        compact_chunk<SEL_NW>(ok, lane, wave, s_cnt, base, [&](int pos) {
             a.sel[pos] = n;
             a.xy[pos] = (float)x;
             a.xy[a.N + pos] = (float)y;
-        }
-        base += tot;
-        __syncthreads();
+        });
     }
     if (tid == 0) { a.count[0] = base; a.count[1] = tsel; }
 }
@@ -119,14 +108,8 @@ __global__ void extract_patches_nhwc_kernel(const float *fmap, int ldf, int C, i
                                             const int32_t *count_dev, int cap, float *patches) {
     const int i = blockIdx.x;
     if (i >= min(*count_dev, cap)) return;
-    const int left = (int)floorf(xy[i] * cscale - 2.0f), top = (int)floorf(xy[ldxy + i] * cscale - 2.0f);
-    for (int e = threadIdx.x; e < C * 16; e += blockDim.x) {
-        const int c = e % C, t = e / C, r = t >> 2, w = t & 3;  // lanes sweep channels: contiguous reads
-        const int yy = top + r, xx = left + w;
-        float v = 0.f;
-        if (yy >= 0 && yy < H2 && xx >= 0 && xx < W2) v = fmap[((size_t)yy * W2 + xx) * ldf + c];
-        patches[((size_t)i * C + c) * 16 + t] = v;
-    }
+    patch_window(fmap, ldf, C, H2, W2, patch_origin(xy[i], cscale), patch_origin(xy[ldxy + i], cscale), (int)threadIdx.x, (int)blockDim.x,
+                 [&](int c, int t, float v) { patches[((size_t)i * C + c) * 16 + t] = v; });
 }
 
 __global__ void gather_rows_sel_kernel(const float *x, int ldx, int C, const int32_t *row_idx, const int32_t *count_dev, int cap,
@@ -137,46 +120,29 @@ __global__ void gather_rows_sel_kernel(const float *x, int ldx, int C, const int
     for (int c = threadIdx.x; c < C; c += blockDim.x) out[(size_t)i * ldo + c] = x[r * ldx + c];
 }
 
-// one wave per match: 16 cosine similarities (eps 1e-8, torch.cosine_similarity), argmax, fine_xy
+// one wave per match: 16 cosine similarities, argmax, fine_xy
 __global__ __launch_bounds__(64) void fine_match_kernel(const float *patches, const float *pcf, int ldp, int C, const float *xy,
                                                         int ldxy, float cscale, const int32_t *count_dev, int cap, float *fine_xy,
                                                         int32_t *best) {
     const int i = blockIdx.x;
     if (i >= min(*count_dev, cap)) return;
     const int lane = threadIdx.x;
-    const int pxl = lane & 15, part = lane >> 4;  // 4 lanes groups split the channels of one pixel
-    float dot = 0.f, nn = 0.f, pp = 0.f;
-    for (int c = part; c < C; c += 4) {
-        const float pv = patches[((size_t)i * C + c) * 16 + pxl];
-        const float fv = pcf[(size_t)i * ldp + c];
-        dot += pv * fv;
-        nn += pv * pv;
-        pp += fv * fv;
-    }
-    dot += __shfl_xor(dot, 16, 64); dot += __shfl_xor(dot, 32, 64);
-    nn += __shfl_xor(nn, 16, 64); nn += __shfl_xor(nn, 32, 64);
-    pp += __shfl_xor(pp, 16, 64); pp += __shfl_xor(pp, 32, 64);
-    float sim = dot / (fmaxf(sqrtf(nn), 1e-8f) * fmaxf(sqrtf(pp), 1e-8f));
-    int bi = pxl;
-#pragma unroll
-    for (int o = 8; o > 0; o >>= 1) {
-        const float os = __shfl_xor(sim, o, 64);
-        const int oi = __shfl_xor(bi, o, 64);
-        if (os > sim || (os == sim && oi < bi)) { sim = os; bi = oi; }
-    }
+    const int bi = argmax16(fine_cosine16([&](int c, int pxl) { return patches[((size_t)i * C + c) * 16 + pxl]; },
+                                          [&](int c) { return pcf[(size_t)i * ldp + c]; }, C, lane).sim(), lane);
     if (lane == 0) {
         best[i] = bi;
-        // eval_all.py:103-105 — x receives idx // 4 and y receives idx % 4 (kept as in the reference)
-        fine_xy[i] = (xy[i] * cscale - 2.0f) + (float)(bi / 4);
-        fine_xy[cap + i] = (xy[ldxy + i] * cscale - 2.0f) + (float)(bi % 4);
+        const float2 f = fine_xy_pair(xy[i], xy[ldxy + i], cscale, bi);
+        fine_xy[i] = f.x;
+        fine_xy[cap + i] = f.y;
     }
 }
 
 // Everything of a test-mode forward that follows the match selection (network.py:153-161 + eval_all.py:99-105), one workgroup per
 // accepted match i (count read on the device): the coarse point, its nearest stage-1 node (point2node, network.py:250-264: canonical
 // distance, lowest index on ties - the (distance, index) key of nearest_kernel), that node's fine descriptor, the 4 x 4 patch of the
-// fine image map under the coarse pixel and the fine matching of the two.  Same per-element arithmetic, in the same order, as the five
-// stand-alone kernels above / in knn.hip: bit-identical outputs, four launches fewer on a frame's chain.
+// fine image map under the coarse pixel and the fine matching of the two.  Every step is the body the five stand-alone kernels above /
+// in knn.hip run (match_parts.h: nearest_scan, patch_window, fine_cosine16, argmax16, fine_xy_pair), fed from LDS where they read
+// global memory: bit-identical outputs, four launches fewer on a frame's chain.
 struct FinishArgs {
     const float *pts4, *pts1, *fmap, *xy, *fpc;
     const int32_t *sel, *count;
@@ -203,42 +169,14 @@ __global__ __launch_bounds__(256) void match_finish_kernel(FinishArgs a) {
     const float qx = a.pts4[3 * n], qy = a.pts4[3 * n + 1], qz = a.pts4[3 * n + 2];
     if (tid < 3) a.coarse_pts[3 * (size_t)i + tid] = a.pts4[3 * n + tid];
     // nearest stage-1 node
-    const float qq = canon_sqnorm(qx, qy, qz);
-    u64 bestk = KEY_INF;
-    for (int c0 = tid; c0 < a.N1; c0 += 1024) {
-        float px[4], py[4], pz[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const int c = min(c0 + 256 * u, a.N1 - 1);
-            px[u] = a.pts1[3 * (size_t)c];
-            py[u] = a.pts1[3 * (size_t)c + 1];
-            pz[u] = a.pts1[3 * (size_t)c + 2];
-        }
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const int c = c0 + 256 * u;
-            const float d = canon_dist(qx, qy, qz, qq, px[u], py[u], pz[u], canon_sqnorm(px[u], py[u], pz[u]));
-            if (c < a.N1) bestk = umin64(bestk, ((u64)__float_as_uint(d) << 32) | (unsigned)c);
-        }
-    }
-    bestk = umin64(bestk, lane_xor64<32>(bestk, lane));
-    bestk = umin64(bestk, lane_xor64<16>(bestk, lane));
-    bestk = umin64(bestk, lane_xor64<8>(bestk, lane));
-    bestk = umin64(bestk, lane_xor64<4>(bestk, lane));
-    bestk = umin64(bestk, lane_xor64<2>(bestk, lane));
-    bestk = umin64(bestk, lane_xor64<1>(bestk, lane));
+    const u64 bestk = wave_min_key(nearest_scan<256>(a.pts1, a.N1, qx, qy, qz, tid));
     if (lane == 0) s_key[wave] = bestk;
     // the patch does not depend on the node: gathered while the keys settle
     const float cx = a.xy[i], cy = a.xy[a.ldxy + i];
-    const int left = (int)floorf(cx * a.cscale - 2.0f), top = (int)floorf(cy * a.cscale - 2.0f);
-    for (int e = tid; e < a.C * 16; e += 256) {
-        const int c = e % a.C, t = e / a.C, r = t >> 2, w = t & 3;  // lanes sweep channels: contiguous reads
-        const int yy = top + r, xx = left + w;
-        float v = 0.f;
-        if (yy >= 0 && yy < a.H2 && xx >= 0 && xx < a.W2) v = a.fmap[((size_t)yy * a.W2 + xx) * a.ldf + c];
+    patch_window(a.fmap, a.ldf, a.C, a.H2, a.W2, patch_origin(cx, a.cscale), patch_origin(cy, a.cscale), tid, 256, [&](int c, int t, float v) {
         a.patches[((size_t)i * a.C + c) * 16 + t] = v;
         s_p[c * 16 + t] = v;
-    }
+    });
     __syncthreads();
     const size_t node = (size_t)(unsigned)(umin64(umin64(s_key[0], s_key[1]), umin64(s_key[2], s_key[3])) & 0xffffffffu);
     for (int c = tid; c < a.C; c += 256) {
@@ -248,31 +186,12 @@ __global__ __launch_bounds__(256) void match_finish_kernel(FinishArgs a) {
     }
     __syncthreads();
     if (wave != 0) return;
-    // fine matching (fine_match_kernel): 16 cosine similarities, 4 lane groups split the channels of one pixel
-    const int pxl = lane & 15, part = lane >> 4;
-    float dot = 0.f, nn = 0.f, pp = 0.f;
-    for (int c = part; c < a.C; c += 4) {
-        const float pv = s_p[c * 16 + pxl];
-        const float fv = s_f[c];
-        dot += pv * fv;
-        nn += pv * pv;
-        pp += fv * fv;
-    }
-    dot += __shfl_xor(dot, 16, 64); dot += __shfl_xor(dot, 32, 64);
-    nn += __shfl_xor(nn, 16, 64); nn += __shfl_xor(nn, 32, 64);
-    pp += __shfl_xor(pp, 16, 64); pp += __shfl_xor(pp, 32, 64);
-    float sim = dot / (fmaxf(sqrtf(nn), 1e-8f) * fmaxf(sqrtf(pp), 1e-8f));
-    int bi = pxl;
-#pragma unroll
-    for (int o = 8; o > 0; o >>= 1) {
-        const float os = __shfl_xor(sim, o, 64);
-        const int oi = __shfl_xor(bi, o, 64);
-        if (os > sim || (os == sim && oi < bi)) { sim = os; bi = oi; }
-    }
+    const int bi = argmax16(fine_cosine16([&](int c, int pxl) { return s_p[c * 16 + pxl]; }, [&](int c) { return s_f[c]; }, a.C, lane).sim(), lane);
     if (lane == 0) {
         a.best[i] = bi;
-        a.fine_xy[i] = (cx * a.cscale - 2.0f) + (float)(bi / 4);         // eval_all.py:103-105: x receives idx // 4, y idx % 4
-        a.fine_xy[a.cap + i] = (cy * a.cscale - 2.0f) + (float)(bi % 4);
+        const float2 fx = fine_xy_pair(cx, cy, a.cscale, bi);
+        a.fine_xy[i] = fx.x;
+        a.fine_xy[a.cap + i] = fx.y;
     }
 }
 

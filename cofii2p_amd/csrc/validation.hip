@@ -4,7 +4,7 @@
 // submission in one launch, with no host read: capturable in a hipGraph.
 // Integer results (counts, n_true, fine_hits) do not depend on any summation order; the floating-point ones (dist, score statistics)
 // are computed by fixed-order loops and shuffles, so a replay is bit-equal to the eager call.
-#include "common.h"
+#include "match_parts.h"
 
 namespace {
 
@@ -21,23 +21,16 @@ __device__ __forceinline__ int val_index(const void *p, int is64, size_t i, int 
 
 // ---------------------------------------------------------------------------------------------- label gathers of a val-mode forward
 // block (k, f): patches[f, k] (C, 16) = the 4 x 4 window of frame f's pixel-major fine map whose left top is centre - 2 (network.py:213,
-// size / 2 = 2; zero outside the map, as cofi_extract_patches_nhwc), fine_pc[f, k] = row inline_idx[f, k] of frame f's fine point
-// descriptors (zero row for an index outside [0, N1))
+// size / 2 = 2; patch_window, the gather of cofi_extract_patches_nhwc, with a 64-bit origin: a label anywhere in int64 gives zeros),
+// fine_pc[f, k] = row inline_idx[f, k] of frame f's fine point descriptors (zero row for an index outside [0, N1))
 __global__ __launch_bounds__(VAL_NT) void val_gather_kernel(const float *fmap, int ldf, int C, int H2, int W2, const float *fpc, int ldfpc,
                                                             int N1, const void *centers, const void *inline_idx, int is64, int K,
                                                             float *patches, float *fine_pc) {
     const int k = blockIdx.x, f = blockIdx.y;
     const long long cx = val_label(centers, is64, ((size_t)f * 2) * K + k), cy = val_label(centers, is64, ((size_t)f * 2 + 1) * K + k);
-    const long long left = cx - 2, top = cy - 2;
-    fmap += (size_t)f * H2 * W2 * ldf;
     float *po = patches + ((size_t)f * K + k) * C * 16;
-    for (int e = threadIdx.x; e < C * 16; e += VAL_NT) {
-        const int c = e % C, t = e / C, r = t >> 2, w = t & 3;   // lanes sweep channels: contiguous reads
-        const long long yy = top + r, xx = left + w;
-        float v = 0.f;
-        if (yy >= 0 && yy < H2 && xx >= 0 && xx < W2) v = fmap[((size_t)yy * W2 + (size_t)xx) * ldf + c];
-        po[(size_t)c * 16 + t] = v;
-    }
+    patch_window(fmap + (size_t)f * H2 * W2 * ldf, ldf, C, H2, W2, cx - 2, cy - 2, (int)threadIdx.x, VAL_NT,
+                 [&](int c, int t, float v) { po[(size_t)c * 16 + t] = v; });
     const long long row = val_label(inline_idx, is64, (size_t)f * K + k);
     const bool ok = row >= 0 && row < N1;
     for (int c = threadIdx.x; c < C; c += VAL_NT)
@@ -64,16 +57,6 @@ __device__ __forceinline__ unsigned val_ordered(float v) {
 }
 __device__ __forceinline__ float val_unordered(unsigned o) { return __uint_as_float((o & 0x80000000u) ? (o & 0x7fffffffu) : ~o); }
 
-__device__ __forceinline__ unsigned long long val_wave_min64(unsigned long long k) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const unsigned hi = __shfl_xor((unsigned)(k >> 32), o, 64), lo = __shfl_xor((unsigned)k, o, 64);
-        const unsigned long long other = ((unsigned long long)hi << 32) | lo;
-        k = other < k ? other : k;
-    }
-    return k;
-}
-
 // train.py:84: sqrt(dx^2 + dy^2) <= dist_thres.  The ONE place the mask is evaluated (the debug output and the true set both call it),
 // every operation a separately rounded one whatever the compiler's contraction setting
 __device__ __forceinline__ bool val_mask(float ix, float iy, float px, float py, float thres) {
@@ -97,31 +80,12 @@ __global__ __launch_bounds__(VAL_NT) void val_monitors_kernel(ValArgs a) {
     const int f = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int K = a.K;
     if (blockIdx.y == 1) {
-        // ---- fine recall (train.py:268-280): per key point the arg-max of 16 cosine similarities (the arithmetic and the first-index
-        // tie rule of cofi_fine_match) against relative_index = (fine_xy - centre + 2) folded as y * 4 + x
-        const int pxl = lane & 15, part = lane >> 4;
+        // ---- fine recall (train.py:268-280): per key point the pick of cofi_fine_match (its fine_cosine16 + argmax16) against
+        // relative_index = (fine_xy - centre + 2) folded as y * 4 + x
         int hits = 0;
         for (int k = wave; k < K; k += VAL_NW) {
             const float *pt = a.patches + ((size_t)f * K + k) * a.C2 * 16, *pf = a.fine_pc + ((size_t)f * K + k) * a.C2;
-            float dot = 0.f, nn = 0.f, pp = 0.f;
-            for (int c = part; c < a.C2; c += 4) {
-                const float pv = pt[(size_t)c * 16 + pxl];
-                const float fv = pf[c];
-                dot += pv * fv;
-                nn += pv * pv;
-                pp += fv * fv;
-            }
-            dot += __shfl_xor(dot, 16, 64); dot += __shfl_xor(dot, 32, 64);
-            nn += __shfl_xor(nn, 16, 64); nn += __shfl_xor(nn, 32, 64);
-            pp += __shfl_xor(pp, 16, 64); pp += __shfl_xor(pp, 32, 64);
-            float sim = dot / (fmaxf(sqrtf(nn), 1e-8f) * fmaxf(sqrtf(pp), 1e-8f));
-            int bi = pxl;
-#pragma unroll
-            for (int o = 8; o > 0; o >>= 1) {
-                const float os = __shfl_xor(sim, o, 64);
-                const int oi = __shfl_xor(bi, o, 64);
-                if (os > sim || (os == sim && oi < bi)) { sim = os; bi = oi; }
-            }
+            const int bi = argmax16(fine_cosine16([&](int c, int pxl) { return pt[(size_t)c * 16 + pxl]; }, [&](int c) { return pf[c]; }, a.C2, lane).sim(), lane);
             const size_t ix = ((size_t)f * 2) * K + k, iy = ((size_t)f * 2 + 1) * K + k;
             const long long rx = val_label(a.fine_xy, a.is64, ix) - val_label(a.fine_center, a.is64, ix) + 2;
             const long long ry = val_label(a.fine_xy, a.is64, iy) - val_label(a.fine_center, a.is64, iy) + 2;
@@ -229,7 +193,7 @@ __global__ __launch_bounds__(VAL_NT) void val_monitors_kernel(ValArgs a) {
         if (lane < K) k0 = ((unsigned long long)val_ordered(s_dist[(size_t)i * K + lane]) << 32) | (unsigned)lane;
         if (lane + 64 < K) k1 = ((unsigned long long)val_ordered(s_dist[(size_t)i * K + lane + 64]) << 32) | (unsigned)(lane + 64);
         for (int p = 0; p < a.topk; ++p) {
-            const unsigned long long m = val_wave_min64(k0 < k1 ? k0 : k1);
+            const unsigned long long m = wave_min_key(k0 < k1 ? k0 : k1);
             if (lane == 0) s_cand[i * VAL_MAXTOP + p] = val_unordered((unsigned)(m >> 32));
             if (k0 == m) k0 = ~0ull;   // keys are unique (the column is part of them): exactly one entry leaves
             if (k1 == m) k1 = ~0ull;
@@ -246,17 +210,7 @@ __global__ __launch_bounds__(VAL_NT) void val_monitors_kernel(ValArgs a) {
             d = s_dist[e];
             ok = val_mask(s_ix[i], s_iy[i], s_px[j], s_py[j], a.dist_thres) && d != 0.f;
         }
-        const unsigned long long m = __ballot(ok);
-        if (lane == 0) s_cnt[wave] = __popcll(m);
-        __syncthreads();
-        int off = base, tot = 0;
-        for (int w = 0; w < VAL_NW; ++w) {
-            if (w < wave) off += s_cnt[w];
-            tot += s_cnt[w];
-        }
-        if (ok) s_true[off + __popcll(m & ((1ull << lane) - 1ull))] = d;
-        base += tot;
-        __syncthreads();
+        compact_chunk<VAL_NW>(ok, lane, wave, s_cnt, base, [&](int pos) { s_true[pos] = d; });
     }
     const int n_true = base;
     // ---- membership BY VALUE (train.py:95-101: `candidate in true_value_list`): one wave per candidate scans the list

@@ -1248,8 +1248,8 @@ def fine_match(patches, pc_feats, xy, cnt, center_scale: float):
 
 def match_finish(pts4, pts1, sel, cnt, fmap, H2: int, W2: int, xy, fine_pc_all, center_scale: float, frames: int = 1):
     """The tail of a test-mode forward in one launch (cofi_match_finish): -> coarse_pts (cap,3), patches (cap,C,16), fine_pc (cap,C),
-    fine_xy (2,cap), best (cap,) - bit-identical to gather_points_sel + nearest_node_sel + gather_rows_sel + extract_patches_nhwc +
-    fine_match.  frames > 1 (stack mode: every input holds `frames` equally sized blocks; sel (frames, cap), xy (frames, 2, cap), cnt (frames, 2)):
+    fine_xy (2,cap), best (cap,) - the outputs of gather_points_sel + nearest_node_sel + gather_rows_sel + extract_patches_nhwc +
+    fine_match, bit for bit: the kernels share their device bodies (csrc/match_parts.h).  frames > 1 (stack mode: every input holds `frames` equally sized blocks; sel (frames, cap), xy (frames, 2, cap), cnt (frames, 2)):
     the outputs gain a leading frame axis."""
     lib = _lib.load()
     _mat(fmap, "fmap"), _mat(fine_pc_all, "fine_pc_all")

@@ -639,15 +639,19 @@ def test_matching_chain(ops, mg):
     assert np.array_equal(fxy.cpu().numpy(), mg["fm_xy"])
 
 
-def test_match_finish_equals_the_five_kernels(ops):
+@pytest.mark.parametrize("N1,C,N4,n,H2,W2", [
+    (1500, 64, 160, 97, 40, 128),
+    (1, 1, 4, 3, 4, 4),           # one node: every load of the scan is the clamped one; one channel; a map as small as the window
+    (255, 13, 16, 9, 8, 12),      # below one 256-wide sub-round of the fused scan, four of the stand-alone one; C % 4 != 0
+    (1025, 128, 64, 64, 40, 128),  # one candidate in the fused scan's second 1024-candidate round; C = FIN_MAXC; count == capacity
+])
+def test_match_finish_equals_the_five_kernels(ops, N1, C, N4, n, H2, W2):
     """cofi_match_finish (coarse point + point2node + fine descriptor + 4x4 patch + fine matching in one launch) against the chain of
     the five stand-alone kernels: bit-identical, incl. patches over the image border and distance ties in the node search"""
     g = torch.Generator().manual_seed(11)
-    N4, N1, C, H2, W2 = 160, 1500, 64, 40, 128
     pts1 = torch.round(torch.randn(N1, 3, generator=g) * 4) / 4          # a lattice: exact distance ties
-    pts4 = pts1[torch.randperm(N1, generator=g)[:N4]] + torch.round(torch.randn(N4, 3, generator=g)) / 8
+    pts4 = pts1[torch.randperm(max(N1, N4), generator=g)[:N4] % N1] + torch.round(torch.randn(N4, 3, generator=g)) / 8
     fmap, fpc = torch.randn(H2 * W2, C, generator=g), torch.randn(N1, C, generator=g)
-    n = 97
     sel = torch.full((N4,), 0, dtype=torch.int32)
     sel[:n] = torch.sort(torch.randperm(N4, generator=g)[:n]).values.int()
     xy = torch.zeros(2, N4)

@@ -172,6 +172,46 @@ def test_monitors_kernel_limits():
     torch.cuda.synchronize()
 
 
+@pytest.mark.parametrize("idt", [torch.int64, torch.int32])
+@pytest.mark.parametrize("C", [1, 13, 128])
+def test_val_gather_against_padded_slices(C, idt):
+    """cofi_val_gather on its own: windows that leave the map on every side, centres far outside it (2**40 as int64) and row indices
+    outside [0, N1) against zero-padding and slicing on the CPU, exactly; and, as both run one window body, against
+    extract_patches_nhwc / gather_rows per frame"""
+    from cofii2p_amd import ops
+
+    B, K, H2, W2, N1, PAD = 3, 7, 6, 10, 50, 8
+    g = torch.Generator().manual_seed(1000 + C)
+    fmap, fpc = torch.randn(B * H2 * W2, C, generator=g), torch.randn(B * N1, C, generator=g)
+    far = 2 ** 40 if idt == torch.int64 else 7
+    xs, ys, rows = [-1, 0, 1, W2 - 1, W2 + 3, 4, far], [H2 + 3, H2 - 1, 1, 0, -1, 2, 3], [-1, N1, 0, N1 - 1, 17, 3, 42]
+    ctr = torch.tensor([[xs[-f:] + xs[:-f], ys[-2 * f:] + ys[:-2 * f]] for f in range(B)])
+    if idt == torch.int64:
+        ctr[2, 1, ctr[2, 0] == 4] = -far     # ... and in y, on the other side
+    idx = torch.tensor([rows[-f:] + rows[:-f] for f in range(B)])
+    pat, fp = ops.val_gather(fmap.to(DEV), H2, W2, fpc.to(DEV), ctr.to(idt).to(DEV), idx.to(idt).to(DEV))
+    padded = torch.nn.functional.pad(fmap.reshape(B, H2, W2, C), (0, 0, PAD, PAD, PAD, PAD))
+    want_pat, want_fp = torch.zeros(B, K, C, 16), torch.zeros(B, K, C)
+    for f in range(B):
+        for k in range(K):
+            x, y, r = int(ctr[f, 0, k]), int(ctr[f, 1, k]), int(idx[f, k])
+            if 2 - PAD <= x <= W2 + PAD - 2 and 2 - PAD <= y <= H2 + PAD - 2:
+                want_pat[f, k] = padded[f, y - 2 + PAD:y + 2 + PAD, x - 2 + PAD:x + 2 + PAD].permute(2, 0, 1).reshape(C, 16)
+            if 0 <= r < N1:
+                want_fp[f, k] = fpc[f * N1 + r]
+    assert torch.equal(pat.cpu(), want_pat) and torch.equal(fp.cpu(), want_fp)
+    assert int((want_pat.abs().sum((2, 3)) == 0).sum()) >= B and int((want_pat != 0).sum()) > 0
+    cnt = torch.tensor([K, 0], dtype=torch.int32, device=DEV)
+    for f in range(B):
+        near = (ctr[f, 0] >= -2) & (ctr[f, 0] < W2 + 2) & (ctr[f, 1] >= -2) & (ctr[f, 1] < H2 + 2)
+        xy = torch.where(near, ctr[f], 0).float().to(DEV)
+        one = ops.extract_patches_nhwc(fmap[f * H2 * W2:(f + 1) * H2 * W2].to(DEV), H2, W2, xy, cnt, K, 1.0)
+        assert int(near.sum()) >= 3 and torch.equal(pat[f][near.to(DEV)], one[near.to(DEV)])
+        valid = (idx[f] >= 0) & (idx[f] < N1)
+        got = ops.gather_rows(fpc[f * N1:(f + 1) * N1].to(DEV), idx[f][valid].int().to(DEV))
+        assert torch.equal(fp[f][valid.to(DEV)], got)
+
+
 # ------------------------------------------------------------------------------------------ fixture frames
 def _fixture_frames(gold, n=6):
     out = []
