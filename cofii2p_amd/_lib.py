@@ -69,6 +69,7 @@ SIGNATURES = {
     "cofi_gemm_f32_stat_slabs": (_I, [_I, _I, _I]),
     "cofi_gemm_f32_colstats": (_I, [_P, _I, _P, _I, _P, _I, _I, _I, _I, _P, _P, _I, _P, _P, _Z, _P]),
     "cofi_gemm_f32_fused": (_I, [_P, _I, _N, _P, _I, _P, _I, _I, _I, _I, _P, _P, _I, _P, _I, _P, _Z, _I, _P]),
+    "cofi_gemm_f32_fused_res": (_I, [_P, _I, _N, _P, _I, _P, _I, _I, _I, _I, _P, _P, _I, _P, _I, _P, _Z, _I, _P, _I, _P, _I, _I, _P]),
     "cofi_gemm_f32_layernorm": (_I, [_P, _I, _P, _I, _P, _I, _I, _I, _I, _P, _P, _P, _F, _I, _P, _I, _P, _Z, _P]),
     "cofi_group_stats_from_colpart": (_I, [_P, _I, _I, _I, _I, _F, _P, _I, _P]),
     "cofi_col_inv_norm_from_colpart": (_I, [_P, _I, _I, _I, _I, _F, _P, _I, _P]),

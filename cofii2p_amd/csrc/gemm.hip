@@ -39,6 +39,10 @@ struct GemmArgs {
     float *colpart;                    // optional (nslab, N, 2)
     const float *ln_gamma, *ln_beta;   // optional fused LayerNorm over the N columns of a row
     const float *res;                  // optional residual added after the LayerNorm
+    // optional row index of the residual (cofi_gemm_f32_fused_res): output row m of frame f = m / res_out_rows takes residual row
+    // f * res_rows + res_idx[m * res_idx_stride]; an index outside [0, res_rows) is a shadow point, its residual is zero (res_src_row)
+    const int32_t *res_idx;
+    int res_idx_stride, res_rows, res_out_rows;
     int lda, ldw, ldc, ldr, M, N, K, act, ksplit, kchunk, ln_relu;
     float ln_eps;
     int bf16x3;
@@ -183,6 +187,41 @@ __device__ __forceinline__ void colstat_fold(const GemmArgs &g, float *red, cons
     }
 }
 
+// Residual source row of output row `row` (< M).  No index table: the row itself.  With one (GemmArgs::res_idx): frame-local, as
+// gather_rows_kernel; for a shadow index row 0 of the frame is addressed (always valid) and `ok` comes back false - the caller puts zeros
+// in its place.
+__device__ __forceinline__ int res_src_row(const GemmArgs &g, int row, bool &ok) {
+    ok = true;
+    if (!g.res_idx) return row;   // uniform
+    const int src = g.res_idx[(size_t)row * g.res_idx_stride];
+    ok = (unsigned)src < (unsigned)g.res_rows;
+    return (row / g.res_out_rows) * g.res_rows + (ok ? src : 0);   // < frames * res_rows (host-checked to fit an int)
+}
+
+// The residual rows of one 64-row slab for the lean epilogues of the 256 x 128 kernels: dst[p] = residual of row row0 + p * RPP, columns
+// col .. col + 3 (one float4: the caller checked ldr % 4 and the base alignment).  Rows past M read the clamped row M - 1 - they are never
+// stored - and, with an index table, the index of that clamped row (the table has M entries); a shadow index gives zeros.
+template <int NP, int RPP>
+__device__ __forceinline__ void load_res_slab(const GemmArgs &g, int row0, int col, float (&dst)[NP][4]) {
+    if (g.res_idx) {   // uniform
+#pragma unroll
+        for (int p = 0; p < NP; ++p) {
+            bool ok;
+            const int src = res_src_row(g, min(row0 + p * RPP, g.M - 1), ok);
+            const f32x4 t = *reinterpret_cast<const f32x4 *>(g.res + (size_t)src * g.ldr + col);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) dst[p][e] = ok ? t[e] : 0.f;
+        }
+    } else {
+#pragma unroll
+        for (int p = 0; p < NP; ++p) {
+            const f32x4 t = *reinterpret_cast<const f32x4 *>(g.res + (size_t)min(row0 + p * RPP, g.M - 1) * g.ldr + col);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) dst[p][e] = t[e];
+        }
+    }
+}
+
 // The straight-line form of the row-wise epilogue (no fused LayerNorm / L2 normalisation, whole float4 columns inside N, aligned output):
 // x[p][e] = value of row row0 + p * RPP, column col + e.  Every option is a workgroup-uniform scalar and guards a whole BLOCK of the
 // NP x 4 elements (a guard around a single element gets if-converted: the compiler then runs e.g. the 10-instruction division for every
@@ -301,8 +340,10 @@ __device__ __forceinline__ EpiRows<ROWS / (NT / (BN / 4))> epi_load_rows(const G
 #pragma unroll
         for (int e = 0; e < 4; ++e) r.rs[p][e] = 0.f;
         if (g.res && rin) {
-            const float *rp = g.res + (size_t)row * g.ldr + col;
-            if (res_vec) {
+            bool rok;
+            const float *rp = g.res + (size_t)res_src_row(g, row, rok) * g.ldr + col;
+            if (!rok) {   // shadow index: the zeros above
+            } else if (res_vec) {
                 const float4 t = *reinterpret_cast<const float4 *>(rp);
                 r.rs[p][0] = t.x; r.rs[p][1] = t.y; r.rs[p][2] = t.z; r.rs[p][3] = t.w;
             } else {
@@ -1519,8 +1560,12 @@ int set_a_norm(GemmArgs &g, const cofi_norm_desc_t *a_norm, int channels, int a_
 
 int gemm_entry(const float *A, int lda, const cofi_norm_desc_t *a_norm, const float *W, int ldw, float *C, int ldc, int M, int N, int K,
                const float *bias, const float *rowdiv, int act, float *colpart, int stat_width, void *ws, size_t ws_bytes, int frames,
-               cofi_stream_t stream) {
+               cofi_stream_t stream, const float *res = nullptr, int ldr = 0, const int32_t *res_idx = nullptr, int res_idx_stride = 0,
+               int res_rows = 0) {
     if (int rc = check_common(A, lda, W, ldw, C, ldc, M, N, K)) return rc;
+    if ((res_idx && !res) || (res && ldr < N)) return COFI_EINVAL;
+    if (res_idx && (res_rows <= 0 || res_idx_stride <= 0 || frames <= 0 || M % frames)) return COFI_EINVAL;
+    if (res_idx && (long)frames * res_rows > 0x7fffffffL) return COFI_EINVAL;   // res_src_row computes the source row as an int
     if (M == 0) return 0;
     const int bf16x3 = (act & COFI_GEMM_BF16X6) ? 2 : ((act & COFI_GEMM_BF16X3) ? 1 : 0);
     const int wsplit = (act & COFI_GEMM_W_SPLIT) ? 1 : 0;
@@ -1546,6 +1591,8 @@ int gemm_entry(const float *A, int lda, const cofi_norm_desc_t *a_norm, const fl
     g.bf16x3 = bf16x3; g.wsplit = wsplit; g.w_lo_off = (long)N * ldw; g.cv_Pout = 1; g.stat_shift = sshift;
     g.asplit = asplit; g.a_lo_off = (long)M * lda;
     g.l2n = l2n;
+    g.res = res; g.ldr = ldr;
+    if (res_idx) { g.res_idx = res_idx; g.res_idx_stride = res_idx_stride; g.res_rows = res_rows; g.res_out_rows = M / frames; }
     if (f16 && p.big && wf16 && f16_two_per_cu(M, N, K, p)) p.bm = 128;
     if (f16 && p.big) {   // the tile flags live behind this plan's split-K partials; a workspace without room for them: the six-product kernel
         const size_t off = p.ksplit > 1 ? (size_t)p.ksplit * M * N * sizeof(float) : 0;
@@ -1698,6 +1745,14 @@ extern "C" int cofi_gemm_f32_fused(const float *A, int lda, const cofi_norm_desc
                                    int M, int N, int K, const float *bias, const float *rowdiv, int act, float *colpart, int stat_width,
                                    void *ws, size_t ws_bytes, int frames, cofi_stream_t stream) {
     return gemm_entry(A, lda, a_norm, W, ldw, C, ldc, M, N, K, bias, rowdiv, act, colpart, stat_width, ws, ws_bytes, frames, stream);
+}
+
+extern "C" int cofi_gemm_f32_fused_res(const float *A, int lda, const cofi_norm_desc_t *a_norm, const float *W, int ldw, float *C, int ldc,
+                                       int M, int N, int K, const float *bias, const float *rowdiv, int act, float *colpart, int stat_width,
+                                       void *ws, size_t ws_bytes, int frames, const float *res, int ldr, const int32_t *res_idx,
+                                       int res_idx_stride, int res_rows, cofi_stream_t stream) {
+    return gemm_entry(A, lda, a_norm, W, ldw, C, ldc, M, N, K, bias, rowdiv, act, colpart, stat_width, ws, ws_bytes, frames, stream, res, ldr,
+                      res_idx, res_idx_stride, res_rows);
 }
 
 extern "C" int cofi_gemm_f32_layernorm(const float *A, int lda, const float *W, int ldw, float *C, int ldc, int M, int N, int K,

@@ -370,14 +370,7 @@ __global__ __launch_bounds__(256, 1) void gemm_x6_big_kernel(GemmArgs g) {
 #pragma unroll
                 for (int e = 0; e < 4; ++e) rs[p][e] = rs_next[p][e] = 0.f;
             auto load_res = [&](int h, float (&dst)[NP][4]) __attribute__((always_inline)) {
-                if constexpr (RES) {
-#pragma unroll
-                    for (int p = 0; p < NP; ++p) {
-                        const f32x4 t = *reinterpret_cast<const f32x4 *>(g.res + (size_t)min(m0 + 64 * h + p * RPP + tr, g.M - 1) * g.ldr + col);
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) dst[p][e] = t[e];
-                    }
-                }
+                if constexpr (RES) load_res_slab<NP, RPP>(g, m0 + 64 * h + tr, col, dst);
             };
             load_res(0, rs);
             __syncthreads();   // every wave is done with the operand stages

@@ -21,6 +21,27 @@ FUSED_KPCONV = os.environ.get("COFI_KPCONV_FUSED", "0") == "1"
 # plane stores cost what the GEMMs win).  COFI_KPCONV_AGG_PLANES=0 / =all forces never / always (A/B runs, tests).
 AGG_PLANES = os.environ.get("COFI_KPCONV_AGG_PLANES", "stack")
 AGG_PLANES_MIN_FRAMES = 4
+# The FPN decoders (kp_backbone.py:111-124) are Linear(cat[nearest_upsample(coarse), stage]).  A Linear commutes with a row gather, so
+# with W = [W_up | W_skip]:  (coarse @ W_up^T)[idx] + stage @ W_skip^T + b - the coarse level (half the rows) is projected BEFORE it is
+# up-sampled and the skip GEMM adds the projected rows by index in its epilogue (ops.gemm(res=, res_idx=)): a third less contraction
+# work per decoder, no gather launch, no concat buffer.  Two accumulations and one add instead of one accumulation: not bit-identical to
+# the concat form (same error against fp64, tests/test_decoders_project_gpu.py).  COFI_DECODER_CONCAT=1: the concat form (A/B runs, tests).
+DECODER_CONCAT = os.environ.get("COFI_DECODER_CONCAT", "0") == "1"
+DECODER_UP = {"decoder4": 2048, "decoder3": 1024, "decoder2": 512}   # columns of the decoder's input that come from the coarser level
+# A decoder whose stage has fewer rows than this (all frames of the submission together) keeps the concat form.  decoder3 alone on the
+# chip (tools/decoder_probe.py, profiles/decoder_project/decoder_probe_*.md): 5120 rows 55.2 us concat / 67.2 us projected, 10240 rows
+# 91.3 / 99.5, 81920 rows 574 / 366 - below 256 tiles of 128 x 128 its coarse GEMM (half the rows, 512 columns, unsplit K = 1024)
+# leaves CUs idle, which the one larger contraction of the concat form does not; 256 tiles = 8192 coarse rows = 16384 rows here.
+# decoder4 and decoder2 win at every measured size.
+DECODER_PROJECT_MIN_ROWS = {"decoder3": 16384}
+
+
+def decoder_weight_unused(key: str) -> bool:
+    """True for the unsplit weight of a decoder that always runs in the projected form (network._pack then skips its bf16 planes)."""
+    for name in DECODER_UP:
+        if key == "pc_encoder.%s.mlp.weight" % name:
+            return not DECODER_CONCAT and DECODER_PROJECT_MIN_ROWS.get(name, 0) <= 0
+    return False
 
 
 def norm_kind(sd) -> str:
@@ -65,6 +86,14 @@ def pack_encoder(sd: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
             out[k] = (v.double() * st[0] + st[1]).float().contiguous()
         else:
             out[k] = v.contiguous()
+    # the decoders' weights split by columns into the part that meets the up-sampled coarser level and the part that meets the stage's own
+    # features ('bn': after the fold, so both halves carry the row scale; the bias stays with the skip GEMM).  The unsplit weight stays
+    # for the concat form.
+    for name, up in DECODER_UP.items():
+        w = out.get("pc_encoder.%s.mlp.weight" % name)
+        if w is not None:
+            out["pc_encoder.%s.mlp.up.weight" % name] = w[:, :up].contiguous()
+            out["pc_encoder.%s.mlp.skip.weight" % name] = w[:, up:].contiguous()
     out["pc_encoder.__norm__"] = kind
     return out
 
@@ -184,17 +213,33 @@ def run_block_plain(P, kind: str, blk: KPBlock, feats, q_pts, s_pts, idx, out=No
     return _unary_plain(P, kind, p + "unary2.", x, LRELU, res=sc, out=out)
 
 
+def _decoder(P, kind: str, name: str, coarse, stage, up_idx, frames: int):
+    """One FPN decoder in the projected form: Linear over [nearest_upsample(coarse) | stage] as a GEMM over the coarse rows and a GEMM over
+    the stage rows whose epilogue adds the projected coarse rows by index - before the GroupNorm statistics ('gn'), the folded BatchNorm's
+    LeakyReLU ('bn') or the LayerNorm ('ln')."""
+    p = "pc_encoder.%s." % name
+    proj = ops.gemm(coarse, P[p + "mlp.up.weight"], frames=frames)
+    w, b = P[p + "mlp.skip.weight"], P[p + "mlp.bias"]
+    if kind == "gn":
+        sw = _gn_width(w.shape[0])
+        y, part = ops.gemm_colstats(stage, w, bias=b, stat_width=sw, frames=frames, res=proj, res_idx=up_idx)
+        return ops.group_norm_apply(y, _stats(y, part, frames, sw), P[p + "norm.norm.weight"], P[p + "norm.norm.bias"], slope=LRELU, frames=frames)
+    if kind == "bn":
+        return ops.gemm(stage, w, bias=b, act=ops.ACT_LEAKY01, frames=frames, res=proj, res_idx=up_idx)
+    return _ln(P, p + "norm.", ops.gemm(stage, w, bias=b, frames=frames, res=proj, res_idx=up_idx), LRELU)
+
+
 def run_fpn(P, points: List[torch.Tensor], neighbors, subsampling, upsampling, feats, taps=None, frames: int = 1, order=None, l2norm_fine: bool = False):
     """`order` (optional): per stage, the frame-local processing order of the stage's points (spatially sorted)."""
     """Returns [latent_s2 (N1,64), latent_s3 (N2,512), latent_s4 (N3,1024), feats_s5 (N4,2048)].
-    The last block of stages 1..3 writes directly into the right part of the decoder's concat
-    buffer (kp_backbone.py:112,117,122 torch.cat)."""
+    The decoders (kp_backbone.py:111-124) run in the projected form (_decoder, DECODER_CONCAT above).  In the concat form the last
+    block of stages 1..3 writes directly into the right part of the decoder's concat buffer (kp_backbone.py:112,117,122 torch.cat)."""
     dev = feats.device
     dec_in = {name: cin for name, cin, _, _ in DECODERS}
-    # concat buffers: [upsampled deeper latent | stage features]
-    cat = {3: torch.empty((points[3].shape[0], dec_in["decoder4"]), dtype=torch.float32, device=dev),
-           2: torch.empty((points[2].shape[0], dec_in["decoder3"]), dtype=torch.float32, device=dev),
-           1: torch.empty((points[1].shape[0], dec_in["decoder2"]), dtype=torch.float32, device=dev)}
+    dec_stage = {"decoder4": 3, "decoder3": 2, "decoder2": 1}   # the stage whose rows a decoder produces
+    # concat form (the switch, or a decoder below its row threshold): buffers [upsampled deeper latent | stage features]
+    cat = {st: torch.empty((points[st].shape[0], dec_in[name]), dtype=torch.float32, device=dev) for name, st in dec_stage.items()
+           if DECODER_CONCAT or points[st].shape[0] < DECODER_PROJECT_MIN_ROWS.get(name, 0)}
     stage_width = {1: 256, 2: 512, 3: 1024}
     last_of_stage = {}
     for blk in ENCODER:
@@ -220,14 +265,23 @@ def run_fpn(P, points: List[torch.Tensor], neighbors, subsampling, upsampling, f
         if taps is not None:
             taps[blk.name] = x
     s5 = stage_out[4]
-    ops.gather_rows(s5, upsampling[3], out=cat[3][:, :2048], frames=frames)
     dec = (lambda name, x_: _unary(P, name, x_, LRELU, frames=frames)) if kind == "gn" else (lambda name, x_: _unary_plain(P, kind, name, x_, LRELU))
-    l4 = dec("pc_encoder.decoder4.", cat[3])
-    ops.gather_rows(l4, upsampling[2], out=cat[2][:, :1024], frames=frames)
-    l3 = dec("pc_encoder.decoder3.", cat[2])
-    ops.gather_rows(l3, upsampling[1], out=cat[1][:, :512], frames=frames)
+
+    def upsampled_cat(name, st, coarse):   # concat form: the coarser latent gathered into the left part of the stage's buffer
+        k = "pc_encoder.%s.mlp.weight" % name
+        P[k] = ops.presplit(P[k])   # the unsplit weights are pre-split on first use: the projected form never reads them
+        ops.gather_rows(coarse, upsampling[st], out=cat[st][:, :DECODER_UP[name]], frames=frames)
+        return cat[st]
+
+    l4 = dec("pc_encoder.decoder4.", upsampled_cat("decoder4", 3, s5)) if 3 in cat else _decoder(P, kind, "decoder4", s5, stage_out[3], upsampling[3], frames)
+    l3 = dec("pc_encoder.decoder3.", upsampled_cat("decoder3", 2, l4)) if 2 in cat else _decoder(P, kind, "decoder3", l4, stage_out[2], upsampling[2], frames)
     # l2norm_fine: the stage-2 latent leaves L2-normalised (network.py:83, its only reader) from this GEMM's epilogue
-    l2 = ops.gemm(cat[1], P["pc_encoder.decoder2.mlp.weight"], bias=P["pc_encoder.decoder2.mlp.bias"], l2norm=l2norm_fine)
+    b2 = P["pc_encoder.decoder2.mlp.bias"]
+    if 1 in cat:
+        l2 = ops.gemm(upsampled_cat("decoder2", 1, l3), P["pc_encoder.decoder2.mlp.weight"], bias=b2, l2norm=l2norm_fine)
+    else:
+        proj = ops.gemm(l3, P["pc_encoder.decoder2.mlp.up.weight"], frames=frames)
+        l2 = ops.gemm(stage_out[1], P["pc_encoder.decoder2.mlp.skip.weight"], bias=b2, frames=frames, l2norm=l2norm_fine, res=proj, res_idx=upsampling[1])
     if taps is not None:
         taps.update(decoder4=l4, decoder3=l3, decoder2=l2)
     return [l2, l3, l4, s5]

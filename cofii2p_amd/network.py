@@ -165,7 +165,8 @@ class CoFiI2P(nn.Module):
 
         for d in [P] + self._layers:   # split once into bf16 hi/lo planes (the bf16x3 kernels read those; fp32 mode reads .w)
             for k in list(d):
-                if gemm_weight(k, d[k]):
+                # (the unsplit weight of a decoder that always runs in the projected form is not read; the concat form splits on first use)
+                if gemm_weight(k, d[k]) and not kpfpn.decoder_weight_unused(k):
                     d[k] = ops.presplit(d[k])
         self._packed, self._packed_key = P, stamp
         return P

@@ -403,7 +403,7 @@ class SplitA:
         self.shape, self.device, self.dtype = (planes.shape[1], K), planes.device, torch.float32
 
 
-def _gemm_impl(a, w, out, bias, rowdiv, act, stat_width, frames, l2norm=False):
+def _gemm_impl(a, w, out, bias, rowdiv, act, stat_width, frames, l2norm=False, res=None, res_idx=None, res_rows=None):
     lib = _lib.load()
     if isinstance(a, Normed) and not isinstance(w, SplitW) and a.fusable():
         w = SplitW(w)   # the normalising loader lives in the pre-split-weight kernels
@@ -438,22 +438,53 @@ def _gemm_impl(a, w, out, bias, rowdiv, act, stat_width, frames, l2norm=False):
     wp, wld, wflag = _wargs(w, None if (l2norm or aflag) else (lambda: lib.cofi_gemm_f16x3_eligible(M, N, K, int(nd is not None), frames) == 1))
     if l2norm and N > 128:
         raise _lib.CofiError("gemm: the L2-normalising epilogue serves N <= 128")
-    rc = lib.cofi_gemm_f32_fused(a_ptr, a_ld, None if nd is None else ctypes.byref(nd), wp, wld, _p(out), _ld(out), M, N, K, _p(bias),
-                                 _p(rowdiv), act | _gemm_flag() | wflag | aflag | (GEMM_L2NORM if l2norm else 0), _p(colpart), max(stat_width, 1), _p(ws), 0 if ws is None else ws.numel(),
-                                 frames, _stream())
-    _lib.check(rc, "cofi_gemm_f32_fused")
+    flags = act | _gemm_flag() | wflag | aflag | (GEMM_L2NORM if l2norm else 0)
+    if res is None:
+        if res_idx is not None:
+            raise _lib.CofiError("gemm: res_idx without res")
+        rc = lib.cofi_gemm_f32_fused(a_ptr, a_ld, None if nd is None else ctypes.byref(nd), wp, wld, _p(out), _ld(out), M, N, K, _p(bias),
+                                     _p(rowdiv), flags, _p(colpart), max(stat_width, 1), _p(ws), 0 if ws is None else ws.numel(),
+                                     frames, _stream())
+        _lib.check(rc, "cofi_gemm_f32_fused")
+        return out, colpart
+    # residual joined in the epilogue; with res_idx (M,) or (M,H) int32 (column 0, as gather_rows) the residual row of output row m is
+    # res[frame(m) * res_rows + res_idx[m]], zero for a shadow index
+    _mat(res, "res")
+    if res.shape[1] != N:
+        raise _lib.CofiError("gemm: residual has %d columns, the output %d" % (res.shape[1], N))
+    istride = 0
+    if res_idx is None:
+        if res.shape[0] != M:
+            raise _lib.CofiError("gemm: residual has %d rows, the output %d" % (res.shape[0], M))
+        res_rows = 0
+    else:
+        if res_idx.dtype != torch.int32 or not res_idx.is_cuda or res_idx.dim() not in (1, 2) or res_idx.shape[0] != M:
+            raise _lib.CofiError("gemm: res_idx must be CUDA int32 (M,) or (M,H)")
+        istride = res_idx.stride(0)
+        if res_rows is None:
+            res_rows = res.shape[0] // frames
+        if res_rows * frames > res.shape[0]:
+            raise _lib.CofiError("gemm: %d frames of %d residual rows exceed the %d rows of res" % (frames, res_rows, res.shape[0]))
+    rc = lib.cofi_gemm_f32_fused_res(a_ptr, a_ld, None if nd is None else ctypes.byref(nd), wp, wld, _p(out), _ld(out), M, N, K, _p(bias),
+                                     _p(rowdiv), flags, _p(colpart), max(stat_width, 1), _p(ws), 0 if ws is None else ws.numel(),
+                                     frames, _p(res), _ld(res), _p(res_idx), istride, res_rows, _stream())
+    _lib.check(rc, "cofi_gemm_f32_fused_res")
     return out, colpart
 
 
-def gemm(a, w, out: Optional[torch.Tensor] = None, bias=None, rowdiv=None, act: int = ACT_NONE, frames: int = 1, l2norm: bool = False):
-    """out[m,n] = act( (a @ w.T)[m,n] / rowdiv[m] + bias[n] );  a (M,K) [or a Normed: normalised on the fly], w (N,K).
+def gemm(a, w, out: Optional[torch.Tensor] = None, bias=None, rowdiv=None, act: int = ACT_NONE, frames: int = 1, l2norm: bool = False,
+         res=None, res_idx=None, res_rows=None):
+    """out[m,n] = act( (a @ w.T)[m,n] / rowdiv[m] + bias[n] + R[m,n] );  a (M,K) [or a Normed: normalised on the fly], w (N,K).
+    R: the optional residual - res[m], or with res_idx ((M,) / (M,H) int32, column 0) res[frame(m) * res_rows + res_idx[m]] with
+    frame-local indices and zero rows for shadow indices (gather_rows' conventions; res_rows defaults to res.shape[0] // frames).
     l2norm (N <= 128): the rows of the result are L2-normalised in the epilogue (F.normalize(dim=1))."""
-    return _gemm_impl(a, w, out, bias, rowdiv, act, 0, frames, l2norm)[0]
+    return _gemm_impl(a, w, out, bias, rowdiv, act, 0, frames, l2norm, res, res_idx, res_rows)[0]
 
 
-def gemm_colstats(a, w, out=None, bias=None, rowdiv=None, act: int = ACT_NONE, stat_width: int = 1, frames: int = 1):
-    """gemm() that also returns the fused statistics partials: (out, colpart (nslab, N // stat_width, 2))."""
-    return _gemm_impl(a, w, out, bias, rowdiv, act, stat_width, frames)
+def gemm_colstats(a, w, out=None, bias=None, rowdiv=None, act: int = ACT_NONE, stat_width: int = 1, frames: int = 1,
+                  res=None, res_idx=None, res_rows=None):
+    """gemm() that also returns the fused statistics partials (taken over the sum with the residual): (out, colpart (nslab, N // stat_width, 2))."""
+    return _gemm_impl(a, w, out, bias, rowdiv, act, stat_width, frames, False, res, res_idx, res_rows)
 
 
 def colstats_frames_ok(M_total: int, N: int, K: int, frames: int) -> bool:

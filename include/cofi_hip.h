@@ -247,6 +247,20 @@ int cofi_gemm_f32_colstats(const float *A, int lda, const float *W, int ldw, flo
 int cofi_gemm_f32_fused(const float *A, int lda, const cofi_norm_desc_t *a_norm, const float *W, int ldw, float *C, int ldc, int M, int N,
                         int K, const float *bias, const float *rowdiv, int act, float *colpart, int stat_width, void *ws, size_t ws_bytes,
                         int frames, cofi_stream_t stream);
+/* cofi_gemm_f32_fused with a RESIDUAL joined in the epilogue, before the activation, the statistics and the L2 normalisation:
+ *   C[m,:] = act( (A W^T)[m,:] / rowdiv[m] + bias + R[m,:] ),   R[m,:] = res[m,:]                                  (res_idx == NULL)
+ *                                                                R[m,:] = res[f * res_rows + res_idx[m * res_idx_stride], :]  otherwise,
+ * f = m / (M / frames) the frame of row m: the indices are frame-local and an index outside [0, res_rows) is a shadow point whose
+ * residual is zero - the conventions of cofi_gather_rows, so Linear(cat[x[idx], y]) = (x W_up^T)[idx] + y W_skip^T + b runs as two
+ * contractions and the gathered matrix never exists (the FPN decoders, model/kpconv/kp_backbone.py:111-124).  res (rows of ldr >= N
+ * floats) holds frames * res_rows rows when indexed, M rows otherwise.  Everything cofi_gemm_f32_fused accepts is accepted; the residual
+ * is added once, by the fold launch, when K is split.  res == NULL: cofi_gemm_f32_fused, bit for bit.
+ * COFI_EINVAL: res_idx without res, ldr < N, and with an index table res_rows <= 0, res_idx_stride <= 0, M % frames != 0 or
+ * frames * res_rows > INT_MAX (source rows are addressed with an int). */
+int cofi_gemm_f32_fused_res(const float *A, int lda, const cofi_norm_desc_t *a_norm, const float *W, int ldw, float *C, int ldc, int M, int N,
+                            int K, const float *bias, const float *rowdiv, int act, float *colpart, int stat_width, void *ws, size_t ws_bytes,
+                            int frames, const float *res, int ldr, const int32_t *res_idx, int res_idx_stride, int res_rows,
+                            cofi_stream_t stream);
 /* Contraction with fused row LayerNorm (N <= 128): C = relu?(LN(A W^T + bias) * gamma + beta) + res.
  * Replaces Linear + nn.LayerNorm (+ residual) of model/transformer/transformer.py:57-58,61-64. */
 int cofi_gemm_f32_layernorm(const float *A, int lda, const float *W, int ldw, float *C, int ldc, int M, int N, int K,
