@@ -136,6 +136,7 @@ SIGNATURES = {
     "cofi_pnp_ransac_batch_workspace": (_Z, [_I, _I]),
     "cofi_pnp_ransac_batch": (_I, [_P, _I, _P, _I, _I, _P, _I, _P, _I, _I, _I, _F, ctypes.c_uint, _I, _P, _Z, _P, _P, _P, _P]),
     "cofi_pose_errors": (_I, [_P, _P, _I, _I, _P, _P]),
+    "cofi_eval_monitors": (_I, [_P, _I, _P, _I, _I, _P, _I, _P, _I, _I, _P, _P, _P, _I, _P, _I, _P, _P, _I, _P]),
     "cofi_val_gather": (_I, [_P, _I, _I, _I, _I, _P, _I, _I, _P, _P, _I, _I, _I, _P, _P, _P]),
     "cofi_val_monitors_workspace": (_Z, [_I, _I]),
     "cofi_val_monitors": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _I, _P, _P, _F, _I, _I, _I, _P, _P, _P, _P, _P, _P,

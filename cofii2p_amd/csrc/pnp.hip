@@ -18,6 +18,7 @@
 //   an accessor, so frame f of a batch executes the arithmetic of the per-frame call in the same order: bit-identical results.
 // Kernel 3 (pose_errors_kernel): RTE / RRE of B poses against ground truth, one thread per frame, fp64.
 #include "common.h"
+#include "pose_errors.h"
 
 namespace {
 
@@ -481,60 +482,12 @@ __global__ __launch_bounds__(256) void pnp_refine_batch_kernel(BatchOperands op,
 }
 
 // ---- registration errors of B poses (evaluation/eval_all.py:16-22): P_diff = inv(P_pred) P_gt, RTE = |t|, RRE = sum |euler 'xzy'| in degrees
+// (pose_errors.h: the body, shared with cofi_eval_monitors)
 template <class T>
 __global__ __launch_bounds__(64) void pose_errors_kernel(const float *pose, const T *P_gt, int frames, double *out) {
     const int f = blockIdx.x * 64 + threadIdx.x;
     if (f >= frames) return;
-    // [P_pred | I] -> [I | inv(P_pred)]: Gauss-Jordan with partial pivoting, fp64.  A general inverse: the refit's R is orthonormal to fp32 only.
-    double A[4][8];
-    for (int r = 0; r < 4; ++r)
-        for (int c = 0; c < 8; ++c) A[r][c] = c < 4 ? (r == c ? 1.0 : 0.0) : (c - 4 == r ? 1.0 : 0.0);
-    for (int r = 0; r < 3; ++r) {
-        for (int c = 0; c < 3; ++c) A[r][c] = (double)pose[12 * f + 3 * r + c];
-        A[r][3] = (double)pose[12 * f + 9 + r];
-    }
-    bool ok = true;
-    for (int col = 0; col < 4; ++col) {
-        int piv = col;
-        for (int r = col + 1; r < 4; ++r)
-            if (fabs(A[r][col]) > fabs(A[piv][col])) piv = r;
-        if (!(fabs(A[piv][col]) > 0.0)) { ok = false; break; }
-        if (piv != col)
-            for (int j = 0; j < 8; ++j) { const double tmp = A[col][j]; A[col][j] = A[piv][j]; A[piv][j] = tmp; }
-        const double d = A[col][col];
-        for (int j = 0; j < 8; ++j) A[col][j] /= d;
-        for (int r = 0; r < 4; ++r) {
-            if (r == col) continue;
-            const double fct = A[r][col];
-            for (int j = 0; j < 8; ++j) A[r][j] -= fct * A[col][j];
-        }
-    }
-    if (!ok) {   // singular P_pred: no error is defined
-        out[2 * f] = out[2 * f + 1] = __builtin_nan("");
-        return;
-    }
-    double D[3][4];   // the three rows of P_diff the errors read
-    for (int r = 0; r < 3; ++r)
-        for (int c = 0; c < 4; ++c) {
-            double acc = 0.0;
-            for (int k = 0; k < 4; ++k) acc += A[r][4 + k] * (double)P_gt[16 * f + 4 * k + c];
-            D[r][c] = acc;
-        }
-    const double rte = sqrt(D[0][3] * D[0][3] + D[1][3] * D[1][3] + D[2][3] * D[2][3]);
-    // scipy's as_euler('xzy') as pose.euler_xzy_deg restates it: R = Ry(c) Rz(b) Rx(a); gimbal lock: third angle zero
-    const double s = D[1][0];
-    const double b = asin(s > 1.0 ? 1.0 : (s < -1.0 ? -1.0 : s));
-    double a, c;
-    if (fabs(s) < 1.0 - 1e-12) {
-        a = atan2(-D[1][2], D[1][1]);
-        c = atan2(-D[2][0], D[0][0]);
-    } else {
-        a = atan2(D[2][1], D[2][2]);
-        c = 0.0;
-    }
-    const double deg = 180.0 / 3.14159265358979323846;
-    out[2 * f] = rte;
-    out[2 * f + 1] = fabs(a * deg) + fabs(b * deg) + fabs(c * deg);
+    pose_errors_frame(pose + 12 * f, P_gt + 16 * f, out + 2 * f, out + 2 * f + 1);
 }
 
 }  // namespace

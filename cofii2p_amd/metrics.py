@@ -4,7 +4,8 @@
     calc_result.py:3-16   registration recall + mean/std of RRE, RTE under (r_thrs, t_thrs)  -> registration_recall / report_lines
     IR_RMSE.py:30-72      inlier ratio per pixel threshold 0..10 step 0.2 and RMSE per frame -> inlier_ratio_rmse / evaluate_result_files
 
-Host-side numpy, like the reference's scripts (a few thousand points per frame: nothing here is worth a kernel).  Pinned against
+Host-side numpy, like the reference's scripts (a few thousand points per frame: nothing here is worth a kernel per frame; a pipeline
+that scores whole stacks without a host round trip uses cofii2p_amd/evaluation.py, which keeps these functions for files).  Pinned against
 the reference's own scripts run on synthetic result files: tests/tools/make_golden_metrics.py -> tests/golden/metrics.npz,
 tests/test_metrics_cpu.py."""
 import os

@@ -474,7 +474,7 @@ class CoFiI2P(nn.Module):
 
     @torch.no_grad()
     def forward_async(self, slot: int, pc_data_dict, img, mode: str = "test", inputs_stable: bool = False, pose_K=None,
-                      pose_iterations: int = 10000, pose_seed: int = 0):
+                      pose_iterations: int = 10000, pose_seed: int = 0, eval_into=None):
         """Enqueue one test-mode forward on the CURRENT stream through the hipGraph of slot `slot` and return
         immediately (no host sync).  `img` (1,3,H,W) = one frame, or (B,3,H,W) with a stack-mode `pc_data_dict`
         (see stack_frames) = B frames through the same launches.  Slots own their static buffers and scratch, so
@@ -492,12 +492,24 @@ class CoFiI2P(nn.Module):
         device-side counts in place; frame f uses seed pose_seed + f) and the handle gains handle["pose"] = {"result" (B,3) int32,
         "R" (B,3,3), "t" (B,3), "inliers" (B,cap) uint8}: device tensors owned by the slot, valid like the other outputs until the slot
         is reused, and complete when `finish(handle)` returns.  A float32 device (B,3,3) pose_K is read in place (keep it unmodified
-        until `finish()`); anything else is copied into a buffer of the slot."""
+        until `finish()`); anything else is copied into a buffer of the slot.
+
+        eval_into=(table, P_gt, row_index) (needs pose_K): the evaluation monitors of every frame (evaluation.eval_monitors, one launch)
+        are enqueued behind the pose tail, before the handle's `done` event: frame f writes row row_index[f] of `table`
+        (evaluation.EvalTable), a negative index nothing.  P_gt (B,4,4) float64 or float32 and row_index (B,) int32 are contiguous device
+        tensors read in place (keep them unmodified until `finish()`).  With the default None nothing about the call, its handle or its
+        captured graphs changes."""
         if mode != "test":
             raise ValueError("forward_async serves the test-mode pipeline")
         _lib.load()
+        if eval_into is not None:
+            from . import evaluation
+
+            if pose_K is None:
+                raise _lib.CofiError("forward_async(eval_into=...): the monitors read the submission's poses - pass pose_K")
+            evaluation.check_eval_into(eval_into, img.shape[0] if img.dim() == 4 else 1, img.device)
         with ops.arithmetic(self.arithmetic):
-            return self._forward_async(slot, pc_data_dict, img, mode, inputs_stable, pose_K, pose_iterations, pose_seed)
+            return self._forward_async(slot, pc_data_dict, img, mode, inputs_stable, pose_K, pose_iterations, pose_seed, eval_into)
 
     def _enqueue_pose(self, slot, outs, K, iterations, seed):
         """the batched pose tail of a submission, on the current stream, into buffers the slot owns"""
@@ -526,9 +538,9 @@ class CoFiI2P(nn.Module):
             K = b["K"]
         res, R, t, mask = _pose.solve_pnp_ransac_batch_into(cpts, fxy, K, cnt[:, 0], b["ws"], b["pose"], b["result"], b["mask"],
                                                             iterations=iterations, seed=seed, coord_major=True)
-        return {"result": res, "R": R, "t": t, "inliers": mask}
+        return {"result": res, "R": R, "t": t, "inliers": mask}, K
 
-    def _forward_async(self, slot, pc_data_dict, img, mode, inputs_stable, pose_K=None, pose_iterations=10000, pose_seed=0):
+    def _forward_async(self, slot, pc_data_dict, img, mode, inputs_stable, pose_K=None, pose_iterations=10000, pose_seed=0, eval_into=None):
         P = self._pack(img.device)
         if inputs_stable:
             for k in ("points", "neighbors", "subsampling", "upsampling"):
@@ -549,7 +561,11 @@ class CoFiI2P(nn.Module):
         if host is None:
             host = hosts[(slot, len(outs))] = torch.empty((len(outs), 2), dtype=torch.int32, pin_memory=True)
         host.copy_(outs[0]["count_all"], non_blocking=True)
-        pose = None if pose_K is None else self._enqueue_pose(slot, outs, pose_K, pose_iterations, pose_seed)
+        pose, K_dev = (None, None) if pose_K is None else self._enqueue_pose(slot, outs, pose_K, pose_iterations, pose_seed)
+        if eval_into is not None:   # the evaluation monitors of the submission: one launch behind the pose tail
+            from . import evaluation
+
+            evaluation.eval_monitors({"out": outs, "pose": pose}, K_dev, eval_into[1], eval_into[0], eval_into[2])
         done = torch.cuda.Event()
         done.record()
         handle = {"out": outs, "count_host": host, "done": done}

@@ -1367,3 +1367,48 @@ def val_monitors(img_desc, pc_desc, W8: int, points4, pc_score, patches, fine_pc
                                None, 0, _stream())
     _lib.check(rc, "cofi_val_monitors")
     return o
+
+
+# ------------------------------------------------------------------------------------------ evaluation pass (csrc/evaluation.hip)
+def eval_monitors(object_points, image_points, count, K, pose, result, P_gt, thresholds, row_index, rows, coord_major: bool = False):
+    """cofi_eval_monitors on B frames, on the current stream: object_points (B, cap, 3), image_points (B, cap, 2) - (B, 2, cap) with
+    coord_major - float32; count: int32 device tensor of B elements (a strided view is read in place) or None = cap; K (B, 3, 3) float32;
+    pose (B, 12) float32 and result (B, 3) int32 as the batched solver writes them; P_gt (B, 4, 4) float64 or float32; thresholds (T,)
+    float64; row_index (B,) int32; rows (table_rows, 6 + T) float64 - all contiguous device tensors.  Frame f writes rows[row_index[f]]
+    (nothing for an index outside the table).  Returns rows."""
+    lib = _lib.load()
+    E = _lib.CofiError
+    if not (torch.is_tensor(object_points) and object_points.is_cuda and object_points.dim() == 3 and object_points.shape[2] == 3):
+        raise E("eval_monitors: object_points must be a CUDA (B,cap,3) tensor - there is no CPU path")
+    B, cap = object_points.shape[0], object_points.shape[1]
+    if B == 0 or cap == 0:
+        raise E("eval_monitors: need B >= 1 frames of capacity >= 1")
+    if not (torch.is_tensor(thresholds) and thresholds.dim() == 1 and thresholds.numel() >= 1):
+        raise E("eval_monitors: thresholds must be a (T,) tensor with T >= 1")
+    T = thresholds.shape[0]
+    if not (torch.is_tensor(rows) and rows.dim() == 2 and rows.shape[0] >= 1 and rows.shape[1] == 6 + T):
+        raise E("eval_monitors: rows must be a (table_rows, 6 + T) = (*, %d) tensor" % (6 + T))
+    if not (torch.is_tensor(P_gt) and P_gt.dtype in (torch.float64, torch.float32)):
+        raise E("eval_monitors: P_gt must be a float64 or float32 tensor")
+    for t, name, shape, dt in ((object_points, "object_points", (B, cap, 3), torch.float32),
+                               (image_points, "image_points", (B, 2, cap) if coord_major else (B, cap, 2), torch.float32),
+                               (K, "K", (B, 3, 3), torch.float32), (pose, "pose", (B, 12), torch.float32),
+                               (result, "result", (B, 3), torch.int32), (P_gt, "P_gt", (B, 4, 4), P_gt.dtype),
+                               (thresholds, "thresholds", (T,), torch.float64), (row_index, "row_index", (B,), torch.int32),
+                               (rows, "rows", tuple(rows.shape), torch.float64)):
+        if not torch.is_tensor(t):
+            raise E("eval_monitors: %s must be a tensor" % name)
+        _label(t, "eval_monitors: " + name, shape, dt)
+        if t.device != object_points.device:
+            raise E("eval_monitors: %s is on another device than object_points" % name)
+    cstride = 0
+    if count is not None:
+        if not (torch.is_tensor(count) and count.is_cuda and count.dtype == torch.int32 and count.dim() == 1 and count.shape[0] == B
+                and (B == 1 or count.stride(0) >= 1)):
+            raise E("eval_monitors: count must be an int32 CUDA tensor of B elements (a strided 1-D view is read in place)")
+        cstride = max(1, count.stride(0))
+    rc = lib.cofi_eval_monitors(_p(object_points), 3 * cap, _p(image_points), 2 * cap, 1 if coord_major else 0, _p(count), cstride, _p(K), cap, B,
+                                _p(pose), _p(result), _p(P_gt), 1 if P_gt.dtype == torch.float64 else 0, _p(thresholds), T, _p(row_index),
+                                _p(rows), rows.shape[0], _stream())
+    _lib.check(rc, "cofi_eval_monitors")
+    return rows

@@ -21,6 +21,10 @@ stack-mode forward (per-frame statistics, frame-local gathers: `tests/test_forwa
 Frames in, poses out (`evaluation/eval_all.py:94-117` at batch rates): `FrameBatcher(model, pose=True)`, `submit(pyr, img, K)` with the
 frame's (3,3) camera matrix, and `pose_result(t)` -> (result (3,) int32 [success, inliers, hypothesis], R (3,3), t (3,), inlier mask of the
 frame's n matches): the poses of a whole stack are solved in one batched pass behind its forward (`forward_async(..., pose_K=...)`).
+
+Frames in, evaluation rows out (`evaluation.evaluate`): `FrameBatcher(model, pose=True, eval_table=table)`, `submit(pyr, img, K, P_gt=...,
+row=i)` with the frame's (4,4) ground-truth pose: the monitors of a stack (`evaluation.eval_monitors`, one launch) run behind its poses and
+frame i lands in row i of the `evaluation.EvalTable`; padding frames write nothing.  `drain()` waits for everything submitted.
 """
 from typing import Dict, List, Optional, Tuple
 
@@ -32,7 +36,7 @@ from .preprocess import FrameStack
 
 class FrameBatcher:
     def __init__(self, model: CoFiI2P, batch: int = 16, streams: int = 4, ring: Optional[int] = None, slot_base: int = 200,
-                 pose: bool = False, pose_iterations: int = 10000):
+                 pose: bool = False, pose_iterations: int = 10000, eval_table=None):
         if batch < 1:
             raise ValueError("batch must be >= 1")
         self.model, self.B = model, int(batch)
@@ -54,6 +58,11 @@ class FrameBatcher:
         self._poses: List[Optional[Dict]] = [None] * self.ring       # handle["pose"] of the stack's finished submission
         self._fine: List[Optional[list]] = [None] * self.ring        # per-frame fine matches (2, n) of that submission
         self._counts: List[Optional[List[int]]] = [None] * self.ring  # matches per frame of that submission
+        if eval_table is not None and not self.pose:
+            raise ValueError("FrameBatcher(eval_table=...): the evaluation monitors read the poses - pass pose=True")
+        self.eval_table = eval_table
+        self._P: List[Optional[torch.Tensor]] = [None] * self.ring   # (B,4,4) float64 device buffer of each stack: the frames' ground-truth poses
+        self._row: List[Optional[torch.Tensor]] = [None] * self.ring  # (B,) int32: the table row of each frame, -1 for padding
 
     # ------------------------------------------------------------------ internals
     def _stream(self, j: int) -> torch.cuda.Stream:
@@ -80,7 +89,11 @@ class FrameBatcher:
     def _launch(self, j: int):
         st = self._stacks[j]
         with torch.cuda.stream(self._stream(j)):
-            if self.pose:
+            if self.eval_table is not None:
+                self._handles[j] = self.model.forward_async(self.slot_base + j, st.pyr, st.img, inputs_stable=True, pose_K=self._K[j],
+                                                            pose_iterations=self.pose_iterations,
+                                                            eval_into=(self.eval_table, self._P[j], self._row[j]))
+            elif self.pose:
                 self._handles[j] = self.model.forward_async(self.slot_base + j, st.pyr, st.img, inputs_stable=True, pose_K=self._K[j],
                                                             pose_iterations=self.pose_iterations)
             else:
@@ -99,12 +112,31 @@ class FrameBatcher:
             raise ValueError("FrameBatcher.submit: K must be a (3,3) camera matrix")
         self._K[j][f].copy_(K, non_blocking=True)
 
-    def submit(self, pc_data_dict: Dict, img: torch.Tensor, K=None) -> Tuple[int, int, int]:
+    def _put_eval(self, j: int, f: int, P_gt, row: int):
+        """the frame's ground-truth pose and table row -> entry f of the stack's buffers (on the submission's stream); a stack that starts
+        has its rows reset to -1, so the padding frames of a flushed stack write nothing"""
+        if self._P[j] is None:
+            dev = self._stacks[j].img.device
+            self._P[j] = torch.zeros((self.B, 4, 4), dtype=torch.float64, device=dev)   # float64 holds a float32 P_gt exactly
+            self._row[j] = torch.full((self.B,), -1, dtype=torch.int32, device=dev)
+        if not torch.is_tensor(P_gt):
+            P_gt = torch.tensor(P_gt, dtype=torch.float64)
+        if tuple(P_gt.shape) != (4, 4):
+            raise ValueError("FrameBatcher.submit: P_gt must be a (4,4) pose matrix")
+        if f == 0:
+            self._row[j].fill_(-1)
+        self._P[j][f].copy_(P_gt, non_blocking=True)
+        self._row[j][f:f + 1].fill_(int(row))
+
+    def submit(self, pc_data_dict: Dict, img: torch.Tensor, K=None, P_gt=None, row: Optional[int] = None) -> Tuple[int, int, int]:
         """one frame -> a ticket.  The frame's tensors are read by a copy kernel enqueued on the submission's stream before this returns
         control to the caller's NEXT enqueue on that stream only - keep them unmodified until `result()` of any later ticket, or pass
-        tensors that are not rewritten (a loader ring).  K: the frame's (3,3) camera matrix (host or device), required with pose=True."""
+        tensors that are not rewritten (a loader ring).  K: the frame's (3,3) camera matrix (host or device), required with pose=True.
+        P_gt, row: the frame's (4,4) ground-truth pose (host or device) and its row of the evaluation table, required with eval_table."""
         if self.pose and K is None:
             raise ValueError("FrameBatcher(pose=True): submit() needs the frame's camera matrix K")
+        if self.eval_table is not None and (P_gt is None or row is None or int(row) < 0):
+            raise ValueError("FrameBatcher(eval_table=...): submit() needs the frame's ground-truth pose P_gt and its table row >= 0")
         j = self._cur
         if self._fill == 0:
             self._collect(j)                      # the stack's previous submission must have been read out before it is overwritten
@@ -125,6 +157,8 @@ class FrameBatcher:
             self._stacks[j].put(self._fill, pyr, feats, img)
             if self.pose:
                 self._put_K(j, self._fill, K)
+            if self.eval_table is not None:
+                self._put_eval(j, self._fill, P_gt, row)
         self._last = (pyr, feats, img)
         ticket = (j, self._serial[j], self._fill)
         self._fill += 1
@@ -146,6 +180,18 @@ class FrameBatcher:
                     self._K[j][f].copy_(self._K[j][self._fill - 1])
         self._launch(j)
         self._cur, self._fill = (j + 1) % self.ring, 0
+
+    def drain(self):
+        """submit what is pending and wait for every submission in flight (their results stay readable as before)"""
+        self.flush()
+        for j in range(self.ring):
+            self._collect(j)
+
+    def reset(self):
+        """wait for every submission in flight and drop a partly filled stack (its frames are not submitted)"""
+        for j in range(self.ring):
+            self._collect(j)
+        self._fill = 0
 
     def result(self, ticket: Tuple[int, int, int]):
         """-> the reference's 8-tuple of the ticket's frame (views of the slot's static outputs; see the module docstring for their lifetime)"""

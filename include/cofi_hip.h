@@ -620,6 +620,25 @@ int cofi_pnp_ransac_batch(const float *obj, int obj_frame_stride, const float *i
  * out (frames, 2) float64 = [RTE = |t(P_diff)|, RRE = sum |euler 'xzy' of R(P_diff)| in degrees, scipy's gimbal convention].
  * pose (frames, 12) as cofi_pnp_ransac writes it; P_gt (frames, 4, 4) row-major, float64 if gt_is_f64 != 0, else float32. */
 int cofi_pose_errors(const float *pose, const void *P_gt, int gt_is_f64, int frames, double *out, cofi_stream_t stream);
+/* The evaluation pass (evaluation/eval_all.py:107-117 and evaluation/IR_RMSE.py:36-59) for the `frames` frames of a stack-mode
+ * submission, behind cofi_pnp_ransac_batch: one launch, one 256-thread workgroup per frame, no host read.  obj, img, count_dev, K_dev,
+ * n_max and their strides are those of cofi_pnp_ransac_batch (a negative count is read as 0); pose (frames, 12) and result (frames, 3)
+ * are that call's outputs; P_gt (frames, 4, 4) row-major, float64 if gt_is_f64 != 0, else float32 (the GT_P of the reference: x_cam =
+ * R_gt x + t_gt); thresholds (T) float64 in DEVICE memory, 1 <= T <= 64 (COFI_EUNSUPPORTED beyond), in any order; row_index (frames)
+ * int32; rows (table_rows, 6 + T) float64.  Frame f writes row row_index[f] of the table and nothing else; an index that is negative
+ * (the padding frames of a flushed stack) or not below table_rows makes the frame leave at once.  The columns of a row:
+ *   0       n        valid correspondences of the frame
+ *   1, 2    success, inliers = result[f, 0], result[f, 1]
+ *   3, 4    RTE, RRE of cofi_pose_errors (the same device function) for this frame's pose; NaN when success == 0
+ *   5       the mean of residual_i = |img_i - gt_pixel_i|, gt_pixel = proj[0:2] / proj[2], proj = K (R_gt x_i + t_gt)  (IR_RMSE.py:58, the
+ *           reference's "RMSE"); NaN when n == 0
+ *   6 + i   the number of residuals <= thresholds[i] (IR_RMSE.py:59 before the division); 0 when n == 0
+ * All arithmetic is fp64; the residual sum is taken in an order that depends on n only, so a frame's row is bit-identical in any batch
+ * and at any position.  A point behind the camera is not special: a NaN residual compares false and makes the mean NaN. */
+int cofi_eval_monitors(const float *obj, int obj_frame_stride, const float *img, int img_frame_stride, int coord_major,
+                       const int32_t *count_dev, int count_stride, const float *K_dev, int n_max, int frames, const float *pose,
+                       const int32_t *result, const void *P_gt, int gt_is_f64, const double *thresholds, int T, const int32_t *row_index,
+                       double *rows, int table_rows, cofi_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * The validation pass of train.py (test_acc, train.py:27-106; fine_recall, :271-281; the pc_score scalars, :256-259) for the `frames`
