@@ -59,6 +59,8 @@ SIGNATURES = {
     "cofi_kp_pack_c4": (_I, [_P, _I, _I, _P, _I, _P, _P]),
     "cofi_kpconv_aggregate_c4": (_I, [_P, _I, _I, _P, _P, _I, _I, _P, _F, _P, _I, _P, _I, _P, _P]),
     "cofi_kpconv_aggregate": (_I, [_P, _I, _I, _I, _P, _P, _P, _I, _I, _P, _F, _P, _P, _I, _I, _P, _I, _P, _P]),
+    "cofi_kp_pack_support": (_I, [_P, _I, _I, _I, _P, _P, _P]),
+    "cofi_kpconv_aggregate_rec": (_I, [_P, _I, _I, _I, _P, _P, _P, _I, _I, _P, _F, _P, _I, _I, _P, _I, _P, _P]),
     "cofi_neighbor_maxpool": (_I, [_P, _I, _I, _I, _P, _I, _I, _P, _I, _I, _P, _P]),
     "cofi_gather_rows": (_I, [_P, _I, _I, _I, _P, _I, _I, _P, _I, _I, _P]),
     "cofi_gemm_f16x3_eligible": (_I, [_I, _I, _I, _I, _I]),
@@ -79,6 +81,8 @@ SIGNATURES = {
     "cofi_group_norm_apply": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _P, _I, _P, _P, _P, _F, _P, _I, _P, _I, _P]),
     "cofi_norm_finalize": (_I, [_N, _I, _I, _P, _P]),
     "cofi_group_norm_apply_partials": (_I, [_P, _I, _I, _I, _N, _P, _I, _N, _P, _I, _P, _I, _P]),
+    "cofi_group_norm_apply_rec": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _P, _I, _P, _P, _P, _F, _P, _I, _P, _P, _I, _P]),
+    "cofi_group_norm_apply_partials_rec": (_I, [_P, _I, _I, _I, _N, _P, _I, _N, _P, _I, _P, _P, _I, _P]),
     "cofi_layer_norm": (_I, [_P, _I, _I, _I, _P, _P, _F, _I, _P, _I, _P, _I, _P]),
     "cofi_layer_norm_act": (_I, [_P, _I, _I, _I, _P, _P, _F, _F, _P, _I, _I, _P, _I, _P]),
     "cofi_loftr_tail_bf16x3": (_I, [_P, _I, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _F, _P, _I, _I, _P]),
@@ -145,6 +149,7 @@ SIGNATURES = {
     "cofi_fine_match": (_I, [_P, _P, _I, _I, _P, _I, _F, _P, _I, _P, _P, _P]),
     "cofi_kpconv_fused_slab_rows": (_I, [_I, _I, _I]),
     "cofi_kpconv_fused": (_I, [_P, _I, _I, _I, _P, _P, _P, _I, _I, _P, _F, _P, _P, _I, _P, _P, _I, _P, _I, _I, _P, _P]),
+    "cofi_kpconv_fused_rec": (_I, [_P, _I, _I, _I, _P, _P, _P, _I, _I, _P, _F, _P, _I, _P, _P, _I, _P, _I, _I, _P, _P]),
     "cofi_color_jitter_chw": (_I, [_P, _I, _I, _P, _F, _F, _F, _F, _P, _Z, _P]),
     "cofi_pack_transform_scan": (_I, [_P, _I, _P, _P, _P]),
     "cofi_voxel_downsample_workspace": (_Z, [_I]),

@@ -38,6 +38,8 @@ struct KpArgs {
     const int32_t *order;          // optional processing order (frame-local query ids, stacked per frame): wave w of the grid
                                    // handles query order[w].  A spatially sorted order makes the waves resident on one CU work on
                                    // neighbouring queries whose neighbour rows overlap, so the gather is served from L1 instead of L2.
+    const float4 *recs;            // REC kernels: one 16-byte record (x, y, z, flag) per support row in place of s_pts / row_pos, flag = 1.0f
+                                   // where the row's feature sum is > 0 (what row_pos holds)
 };
 
 // VEC = contiguous channels one lane loads per neighbour (1, 2 or 4 -> dword / dwordx2 / dwordx4), NCH =
@@ -106,15 +108,28 @@ __device__ __forceinline__ void kp_steps(const char *fbase, const unsigned ldfb,
                     acc[ch][v] = __builtin_amdgcn_mfma_f32_16x16x4f32(w, f.f[ch][v], acc[ch][v], 0, 0, 0);
         };
         // software pipeline: slot k fetches the record of step k+3 (LDS), runs the MFMAs of step k behind it, then issues
-        // the feature loads of step k+3 (L2) - three feature loads stay in flight per wave
+        // the feature loads of step k+3 (L2) - three feature loads stay in flight per wave.  Exactly `steps` steps run (the
+        // support holds 2 - 5 neighbours at the stages with the most queries: one or two steps): a feature load is issued only for
+        // a step that exists, and the rotation is left after the last one.  All tests are wave-uniform (scalar branches); the record
+        // fetches past the last step read shadow records.
         float4 R0 = fetch(0), R1 = fetch(1), R2 = fetch(2), R3;
         KpFeat<VEC, NCH> F0, F1, F2, F3;
-        issue(R0, F0); issue(R1, F1); issue(R2, F2);
-        for (int t = 0; t < steps; t += 4) {  // steps in [steps, roundup4) read shadow records and add zero
+        if (steps > 0) issue(R0, F0);
+        if (steps > 1) issue(R1, F1);
+        if (steps > 2) issue(R2, F2);
+        int t = 0;
+        for (; t + 4 <= steps; t += 4) {   // whole rounds of the rotation
             R3 = fetch(t + 3); consume(R0, F0); issue(R3, F3);
-            R0 = fetch(t + 4); consume(R1, F1); issue(R0, F0);
-            R1 = fetch(t + 5); consume(R2, F2); issue(R1, F1);
-            R2 = fetch(t + 6); consume(R3, F3); issue(R2, F2);
+            R0 = fetch(t + 4); consume(R1, F1); if (t + 4 < steps) issue(R0, F0);
+            R1 = fetch(t + 5); consume(R2, F2); if (t + 5 < steps) issue(R1, F1);
+            R2 = fetch(t + 6); consume(R3, F3); if (t + 6 < steps) issue(R2, F2);
+        }
+        if (t < steps) {   // the last 1 - 3 steps: their loads are in flight, the rotation stands at set 0
+            consume(R0, F0);
+            if (t + 1 < steps) {
+                consume(R1, F1);
+                if (t + 2 < steps) consume(R2, F2);
+            }
         }
     }
 }
@@ -122,7 +137,9 @@ __device__ __forceinline__ void kp_steps(const char *fbase, const unsigned ldfb,
 // The aggregation of ONE query m by one wave (see the file header): acc[ch][v] = MFMA accumulators (rows = kernel points,
 // column j = channel c0 + ch*16*VEC + VEC*j + v), npos = neighbours whose feature row sums to > 0 (kpconv.py:113-114).
 // rec = the wave's private LDS record buffer (PHASE + KP_PAD entries); a is a private copy (frame shift).
-template <int VEC, int NCH, int PHASE>
+// REC: the staging reads ONE 16-byte record per neighbour (a.recs) instead of three position dwords and the flag byte - the
+// same differences, the same list, the same order: identical bits.
+template <int VEC, int NCH, int PHASE, bool REC>
 __device__ __forceinline__ void kp_aggregate_query(KpArgs a, const int m, const int c0, float4 *rec, f32x4 (&acc)[NCH][VEC], int &npos) {
     constexpr int KP_PHASE = PHASE;
     const int lane = threadIdx.x & 63;
@@ -130,8 +147,12 @@ __device__ __forceinline__ void kp_aggregate_query(KpArgs a, const int m, const 
     {   // stack mode: shift the support-side bases to this query's frame (indices are frame-local)
         const size_t fo = (size_t)(m / a.Mpf) * a.N;
         a.feats += fo * a.ldf;
-        a.s_pts += fo * 3;
-        a.row_pos += fo;
+        if constexpr (REC) {
+            a.recs += fo;
+        } else {
+            a.s_pts += fo * 3;
+            a.row_pos += fo;
+        }
     }
     const float qx = a.q_pts[3 * m], qy = a.q_pts[3 * m + 1], qz = a.q_pts[3 * m + 2];
     // MFMA row 15 (lane j == 15) is a padding row that is never stored: it may hold any finite weight
@@ -184,9 +205,15 @@ __device__ __forceinline__ void kp_aggregate_query(KpArgs a, const int m, const 
 #pragma unroll
         for (int r = 0; r < KP_PHASE / 64; ++r) {
             const int idc = (unsigned)idr[r] < (unsigned)a.N ? idr[r] : 0;
-            const float *sp = a.s_pts + 3 * (size_t)idc;
-            px[r] = sp[0]; py[r] = sp[1]; pz[r] = sp[2];
-            pos[r] = a.row_pos[idc];
+            if constexpr (REC) {
+                const float4 rv = a.recs[idc];
+                px[r] = rv.x; py[r] = rv.y; pz[r] = rv.z;
+                pos[r] = rv.w != 0.f;
+            } else {
+                const float *sp = a.s_pts + 3 * (size_t)idc;
+                px[r] = sp[0]; py[r] = sp[1]; pz[r] = sp[2];
+                pos[r] = a.row_pos[idc];
+            }
         }
         int nin = 0;   // neighbours of this phase inside the kernel's support (wave-uniform)
 #pragma unroll
@@ -208,8 +235,10 @@ __device__ __forceinline__ void kp_aggregate_query(KpArgs a, const int m, const 
     }
 }
 
-template <int VEC, int NCH>
-__global__ __launch_bounds__(256) void kpconv_aggregate_kernel(KpArgs a) {
+// amdgpu_waves_per_eu: the occupancy each form had before the step loop got its wave-uniform branches - left alone, the register
+// allocator answers them with a second copy of the accumulators and loses a wave per SIMD (profiles/kpconv_records/README.md).
+template <int VEC, int NCH, bool REC>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(VEC * NCH == 8 ? 4 : (VEC * NCH == 4 ? 6 : 8)))) void kpconv_aggregate_kernel(KpArgs a) {
     __shared__ float4 rec_s[4][KP_PHASE_DEFAULT + KP_PAD];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     // the query id is wave-uniform: keep it (and everything derived from it) in scalar registers
@@ -220,7 +249,7 @@ __global__ __launch_bounds__(256) void kpconv_aggregate_kernel(KpArgs a) {
     const int c0 = blockIdx.y * (16 * VEC * NCH);
     f32x4 acc[NCH][VEC];
     int npos;
-    kp_aggregate_query<VEC, NCH, KP_PHASE_DEFAULT>(a, m, c0, rec_s[wv], acc, npos);
+    kp_aggregate_query<VEC, NCH, KP_PHASE_DEFAULT, REC>(a, m, c0, rec_s[wv], acc, npos);
     // D layout 16x16: row (kernel point) = 4*g + r, col = j  ->  channels c .. c+VEC-1 contiguous
     if (a.planes_lo) {   // bf16 hi / lo planes (same rounding as the GEMM's on-the-fly split: identical products)
         uint16_t *hrow = reinterpret_cast<uint16_t *>(a.agg) + (size_t)m * a.ld_agg;
@@ -284,21 +313,25 @@ __global__ __launch_bounds__(256) void kpconv_aggregate_kernel(KpArgs a) {
 // query are NP waves of ONE workgroup that stage its neighbour records TOGETHER - each wave a 1/NP share of the 128 neighbours,
 // survivors concatenated in neighbour order through LDS - instead of every pass repeating the whole staging.  Same records, same
 // order as kp_aggregate_query: identical bits.
-template <int NP>
-__global__ __launch_bounds__(256) void kpconv_aggregate_shared_kernel(KpArgs a) {
+template <int NP, bool REC>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5))) void kpconv_aggregate_shared_kernel(KpArgs a) {
     constexpr int VEC = 4, NCH = 2, QW = 4 / NP, SH = 128 / NP;   // queries per workgroup, neighbours staged per wave
     __shared__ float4 rec_s[QW][128 + KP_PAD];
     __shared__ int cnt_s[QW][NP], pos_s[QW][NP];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int qs = wv / NP, p = wv % NP;
-    const int j = lane & 15, g = lane >> 4;
+    const int j = lane & 15;
     int m = __builtin_amdgcn_readfirstlane(xcd_contiguous_block(blockIdx.x, gridDim.x) * QW + qs);   // host: M % QW == 0
     if (a.order) m = (m / a.Mpf) * a.Mpf + a.order[m];
     {
         const size_t fo = (size_t)(m / a.Mpf) * a.N;
         a.feats += fo * a.ldf;
-        a.s_pts += fo * 3;
-        a.row_pos += fo;
+        if constexpr (REC) {
+            a.recs += fo;
+        } else {
+            a.s_pts += fo * 3;
+            a.row_pos += fo;
+        }
     }
     const float qx = a.q_pts[3 * m], qy = a.q_pts[3 * m + 1], qz = a.q_pts[3 * m + 2];
     const int jk = j < 15 ? j : 0;
@@ -318,9 +351,18 @@ __global__ __launch_bounds__(256) void kpconv_aggregate_shared_kernel(KpArgs a) 
     const int id = mine ? a.idx[(size_t)m * a.H + hl] : a.N;
     const bool valid = (unsigned)id < (unsigned)a.N;
     const int idc = valid ? id : 0;
-    const float *sp = a.s_pts + 3 * (size_t)idc;
-    const float dx = sp[0] - qx, dy = sp[1] - qy, dz = sp[2] - qz;
-    const int rp = a.row_pos[idc];
+    float px, py, pz;
+    int rp;
+    if constexpr (REC) {
+        const float4 rv = a.recs[idc];
+        px = rv.x; py = rv.y; pz = rv.z;
+        rp = rv.w != 0.f;
+    } else {
+        const float *sp = a.s_pts + 3 * (size_t)idc;
+        px = sp[0]; py = sp[1]; pz = sp[2];
+        rp = a.row_pos[idc];
+    }
+    const float dx = px - qx, dy = py - qy, dz = pz - qz;
     const bool inside = valid && (dx * dx + dy * dy) + dz * dz < rsup2;
     const unsigned long long msk = __ballot(inside);
     const int npos_w = __popcll(__ballot(valid && rp != 0));
@@ -334,6 +376,9 @@ __global__ __launch_bounds__(256) void kpconv_aggregate_shared_kernel(KpArgs a) 
         nin += c;
         npos += pos_s[qs][q];
     }
+    // wave-uniform, but read from LDS: into scalar registers, so that the step loop's tests on nin are scalar branches
+    nin = __builtin_amdgcn_readfirstlane(nin);
+    npos = __builtin_amdgcn_readfirstlane(npos);
     float4 *rec = rec_s[qs];
     if (inside) rec[off + __popcll(msk & ((1ull << lane) - 1ull))] = make_float4(dx, dy, dz, __int_as_float(id));
     if (p == 0) rec[nin + lane] = make_float4(1e18f, 0.f, 0.f, __int_as_float(0));   // shadow records behind the list
@@ -349,11 +394,13 @@ __global__ __launch_bounds__(256) void kpconv_aggregate_shared_kernel(KpArgs a) 
 #pragma unroll
         for (int v = 0; v < VEC; ++v) acc[ch][v] = (f32x4){0.f, 0.f, 0.f, 0.f};
     kp_steps<VEC, NCH>(reinterpret_cast<const char *>(a.feats), 4u * a.ldf, coffb, rec, nin, kx, ky, kz, inv_sigma, acc);
+    // the store addresses are derived from a lane id taken AFTER the step loop, so that nothing of them occupies registers across it
+    const int ls = __lane_id(), js = ls & 15, g = ls >> 4;
     if (a.planes_lo) {   // bf16 hi / lo planes, as kpconv_aggregate_kernel writes them
         uint16_t *hrow = reinterpret_cast<uint16_t *>(a.agg) + (size_t)m * a.ld_agg;
 #pragma unroll
         for (int ch = 0; ch < NCH; ++ch) {
-            const int c = c0 + ch * 16 * VEC + VEC * j;
+            const int c = c0 + ch * 16 * VEC + VEC * js;
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int k = 4 * g + r;
@@ -367,13 +414,13 @@ __global__ __launch_bounds__(256) void kpconv_aggregate_shared_kernel(KpArgs a) 
                 }
             }
         }
-        if (p == 0 && lane == 0) a.cnt[m] = (float)(npos > 1 ? npos : 1);
+        if (p == 0 && ls == 0) a.cnt[m] = (float)(npos > 1 ? npos : 1);
         return;
     }
     float *orow = a.agg + (size_t)m * a.ld_agg;
 #pragma unroll
     for (int ch = 0; ch < NCH; ++ch) {
-        const int c = c0 + ch * 16 * VEC + VEC * j;
+        const int c = c0 + ch * 16 * VEC + VEC * js;
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const int k = 4 * g + r;
@@ -381,7 +428,7 @@ __global__ __launch_bounds__(256) void kpconv_aggregate_shared_kernel(KpArgs a) 
                 *reinterpret_cast<float4 *>(orow + (size_t)k * a.C + c) = make_float4(acc[ch][0][r], acc[ch][1][r], acc[ch][2][r], acc[ch][3][r]);
         }
     }
-    if (p == 0 && lane == 0) a.cnt[m] = (float)(npos > 1 ? npos : 1);
+    if (p == 0 && ls == 0) a.cnt[m] = (float)(npos > 1 ? npos : 1);
 }
 
 // C <= 4 (the first layer of the encoder: [intensity | normal]).  What a neighbour costs in the staging is the number of distinct
@@ -513,7 +560,7 @@ struct KpFusedArgs {
     int qt;                         // queries per workgroup = rows per statistics slab: 16, 32 or 64
 };
 
-template <int MID, int PHASE>
+template <int MID, int PHASE, bool RECS>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) void kpconv_fused_kernel(KpFusedArgs fa) {   // two workgroups per CU
 
     constexpr int VEC = MID / 16, K = 15 * MID, KLD = K + 8, NT = MID / 16, KQ = 8 / NT, KSTEPS = K / 32;
@@ -552,7 +599,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
             m = __builtin_amdgcn_readfirstlane(m);
             f32x4 acc[1][VEC];
             int npos;
-            kp_aggregate_query<VEC, 1, PHASE>(fa.a, m, 0, rec_s[wv], acc, npos);
+            kp_aggregate_query<VEC, 1, PHASE, RECS>(fa.a, m, 0, rec_s[wv], acc, npos);
             // D layout 16x16: row (kernel point) = 4 g + r, column j -> channels VEC j .. VEC j + VEC - 1 of tile row ql
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
@@ -665,6 +712,21 @@ __global__ void row_sum_positive_kernel(const float *feats, int ld, int N, int C
     if (lane == 0) row_pos[n] = s > 0.0f ? 1 : 0;
 }
 
+// rec[n] = (x, y, z, flag): the support record of the REC aggregation kernels for a caller that arrives without one.  The flag is
+// row_sum_positive_kernel's, summed in the same order.
+__global__ void kp_pack_support_kernel(const float *feats, int ld, int N, int C, const float *pts, float4 *rec) {
+    const int n = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (n >= N) return;
+    const int lane = threadIdx.x & 63;
+    float s = 0.f;
+    for (int c = lane; c < C; c += 64) s += feats[(size_t)n * ld + c];
+    s = wave_sum(s);
+    if (lane == 0) {
+        const float *p = pts + 3 * (size_t)n;
+        rec[n] = make_float4(p[0], p[1], p[2], s > 0.0f ? 1.0f : 0.0f);
+    }
+}
+
 // out[m,c] = max_h x[idx[m,h], c], zero row behind idx == N.  One wave per (query, 32-channel chunk):
 // lane (g = l>>3, c4 = l&7) reads float4 #c4 of the chunk for neighbours h = 8i+g, so one load instruction
 // fetches 8 neighbour rows x 128 contiguous bytes; the 8 lane groups are folded with 3 xor-shuffles.
@@ -741,35 +803,62 @@ extern "C" int cofi_row_sum_positive(const float *feats, int ld, int N, int C, u
     return cofi_launch_status();
 }
 
-extern "C" int cofi_kpconv_aggregate(const float *feats, int ldf, int N, int C, const float *q_pts, const float *s_pts,
-                                     const int32_t *idx, int M, int H, const float *kernel_points, float sigma,
-                                     const uint8_t *row_pos, float *agg, int ld_agg, int agg_planes, float *cnt, int frames, const int32_t *order,
-                                     cofi_stream_t stream) {
-    if (!feats || !q_pts || !s_pts || !idx || !kernel_points || !row_pos || !agg || !cnt) return COFI_EINVAL;
-    if (N <= 0 || C <= 0 || M < 0 || H <= 0 || (H & 3) || ldf < C || ld_agg < 15 * C || !(sigma > 0.f) || frames <= 0) return COFI_EINVAL;
-    if (agg_planes && ((ld_agg & 7) || (C & 3) || ((uintptr_t)agg & 15))) return COFI_EINVAL;
+extern "C" int cofi_kp_pack_support(const float *feats, int ldf, int N, int C, const float *points, float *records, cofi_stream_t stream) {
+    if (!feats || !points || !records || N < 0 || C <= 0 || ldf < C || ((uintptr_t)records & 15)) return COFI_EINVAL;
+    if (N == 0) return 0;
+    hipLaunchKernelGGL(kp_pack_support_kernel, dim3(cofi_cdiv(N, 4)), dim3(256), 0, cofi_s(stream), feats, ldf, N, C, points, (float4 *)records);
+    return cofi_launch_status();
+}
+
+// Shape checks and kernel choice of the aggregation; REC: the support arrives as 16-byte records (a.recs) instead of a.s_pts / a.row_pos.
+template <bool REC>
+static int kp_aggregate_launch(KpArgs a, int M, int agg_planes, int frames, cofi_stream_t stream) {
+    const int N = a.N, C = a.C, H = a.H, ldf = a.ldf, ld_agg = a.ld_agg;
+    if (N <= 0 || C <= 0 || M < 0 || H <= 0 || (H & 3) || ldf < C || ld_agg < 15 * C || !(a.sigma > 0.f) || frames <= 0) return COFI_EINVAL;
+    if (agg_planes && ((ld_agg & 7) || (C & 3) || ((uintptr_t)a.agg & 15))) return COFI_EINVAL;
     if ((size_t)N * ldf * 4 >= ((size_t)1 << 32) || N >= (1 << 24) || (size_t)ldf * 4 >= (1u << 24)) return COFI_EUNSUPPORTED;  // 24x24-bit row offsets
     if (M == 0) return 0;
-    KpArgs a{feats, q_pts, s_pts, kernel_points, idx, row_pos, agg, cnt, ldf, N, C, M * frames, H, ld_agg, sigma, M, agg_planes ? (size_t)M * frames * ld_agg : 0, order};
+    a.M = M * frames;
+    a.Mpf = M;
+    a.planes_lo = agg_planes ? (size_t)M * frames * ld_agg : 0;
     M *= frames;
     hipStream_t s = cofi_s(stream);
     const int mb = cofi_cdiv(M, 4);
     if ((C == 256 || C == 512) && (ldf & 3) == 0 && H <= 128 && M % (C == 256 ? 2 : 1) == 0) {
         if (C == 256)
-            hipLaunchKernelGGL(kpconv_aggregate_shared_kernel<2>, dim3(M / 2), dim3(256), 0, s, a);
+            hipLaunchKernelGGL((kpconv_aggregate_shared_kernel<2, REC>), dim3(M / 2), dim3(256), 0, s, a);
         else
-            hipLaunchKernelGGL(kpconv_aggregate_shared_kernel<4>, dim3(M), dim3(256), 0, s, a);
+            hipLaunchKernelGGL((kpconv_aggregate_shared_kernel<4, REC>), dim3(M), dim3(256), 0, s, a);
     } else if ((C & 3) == 0 && (ldf & 3) == 0 && C >= 64) {
         if (C % 128 == 0)
-            hipLaunchKernelGGL((kpconv_aggregate_kernel<4, 2>), dim3(mb, C / 128), dim3(256), 0, s, a);
+            hipLaunchKernelGGL((kpconv_aggregate_kernel<4, 2, REC>), dim3(mb, C / 128), dim3(256), 0, s, a);
         else
-            hipLaunchKernelGGL((kpconv_aggregate_kernel<4, 1>), dim3(mb, cofi_cdiv(C, 64)), dim3(256), 0, s, a);
+            hipLaunchKernelGGL((kpconv_aggregate_kernel<4, 1, REC>), dim3(mb, cofi_cdiv(C, 64)), dim3(256), 0, s, a);
     } else if ((C & 1) == 0 && (ldf & 1) == 0 && C >= 32) {
-        hipLaunchKernelGGL((kpconv_aggregate_kernel<2, 1>), dim3(mb, cofi_cdiv(C, 32)), dim3(256), 0, s, a);
+        hipLaunchKernelGGL((kpconv_aggregate_kernel<2, 1, REC>), dim3(mb, cofi_cdiv(C, 32)), dim3(256), 0, s, a);
     } else {
-        hipLaunchKernelGGL((kpconv_aggregate_kernel<1, 1>), dim3(mb, cofi_cdiv(C, 16)), dim3(256), 0, s, a);
+        hipLaunchKernelGGL((kpconv_aggregate_kernel<1, 1, REC>), dim3(mb, cofi_cdiv(C, 16)), dim3(256), 0, s, a);
     }
     return cofi_launch_status();
+}
+
+extern "C" int cofi_kpconv_aggregate(const float *feats, int ldf, int N, int C, const float *q_pts, const float *s_pts,
+                                     const int32_t *idx, int M, int H, const float *kernel_points, float sigma,
+                                     const uint8_t *row_pos, float *agg, int ld_agg, int agg_planes, float *cnt, int frames, const int32_t *order,
+                                     cofi_stream_t stream) {
+    if (!feats || !q_pts || !s_pts || !idx || !kernel_points || !row_pos || !agg || !cnt) return COFI_EINVAL;
+    KpArgs a{feats, q_pts, s_pts, kernel_points, idx, row_pos, agg, cnt, ldf, N, C, 0, H, ld_agg, sigma, 0, 0, order, nullptr};
+    return kp_aggregate_launch<false>(a, M, agg_planes, frames, stream);
+}
+
+// cofi_kpconv_aggregate with the support as 16-byte records (x, y, z, flag) - (frames * N, 4) floats, written by the GroupNorm apply
+// kernels or cofi_kp_pack_support - in place of s_pts and row_pos: same kernels, same results, one gather per neighbour in the staging.
+extern "C" int cofi_kpconv_aggregate_rec(const float *feats, int ldf, int N, int C, const float *q_pts, const float *records,
+                                         const int32_t *idx, int M, int H, const float *kernel_points, float sigma, float *agg, int ld_agg,
+                                         int agg_planes, float *cnt, int frames, const int32_t *order, cofi_stream_t stream) {
+    if (!feats || !q_pts || !records || !idx || !kernel_points || !agg || !cnt || ((uintptr_t)records & 15)) return COFI_EINVAL;
+    KpArgs a{feats, q_pts, nullptr, kernel_points, idx, nullptr, agg, cnt, ldf, N, C, 0, H, ld_agg, sigma, 0, 0, order, (const float4 *)records};
+    return kp_aggregate_launch<true>(a, M, agg_planes, frames, stream);
 }
 
 // First-layer form (C <= 4): pack [features | position | positive-sum flag] into 32-byte records once, then aggregate from them.
@@ -799,10 +888,11 @@ extern "C" int cofi_kpconv_fused_slab_rows(int C, int M, int frames) {
     return 16;
 }
 
-extern "C" int cofi_kpconv_fused(const float *feats, int ldf, int N, int C, const float *q_pts, const float *s_pts, const int32_t *idx, int M, int H,
-                                 const float *kernel_points, float sigma, const uint8_t *row_pos, const void *w_planes, int ldw, const float *bias,
-                                 float *y, int ldy, float *colpart, int stat_width, int frames, const int32_t *order, cofi_stream_t stream) {
-    if (!feats || !q_pts || !s_pts || !idx || !kernel_points || !row_pos || !w_planes || !y) return COFI_EINVAL;
+template <bool REC>
+static int kp_fused_launch(const float *feats, int ldf, int N, int C, const float *q_pts, const float *s_pts, const float4 *recs, const int32_t *idx,
+                           int M, int H, const float *kernel_points, float sigma, const uint8_t *row_pos, const void *w_planes, int ldw,
+                           const float *bias, float *y, int ldy, float *colpart, int stat_width, int frames, const int32_t *order,
+                           cofi_stream_t stream) {
     if (N <= 0 || M <= 0 || H <= 0 || (H & 3) || ldf < C || ldy < C || !(sigma > 0.f) || frames <= 0) return COFI_EINVAL;
     if (ldw < 15 * C || (ldw & 7) || ((uintptr_t)w_planes & 15)) return COFI_EINVAL;
     const int qt = cofi_kpconv_fused_slab_rows(C, M, frames);
@@ -814,16 +904,33 @@ extern "C" int cofi_kpconv_fused(const float *feats, int ldf, int N, int C, cons
         while ((1 << shift) < stat_width) ++shift;
     }
     KpFusedArgs fa{};
-    fa.a = KpArgs{feats, q_pts, s_pts, kernel_points, idx, row_pos, nullptr, nullptr, ldf, N, C, M * frames, H, 0, sigma, M, 0, order};
+    fa.a = KpArgs{feats, q_pts, s_pts, kernel_points, idx, row_pos, nullptr, nullptr, ldf, N, C, M * frames, H, 0, sigma, M, 0, order, recs};
     fa.w_hi = (const uint16_t *)w_planes;
     fa.w_lo = fa.w_hi + (size_t)C * ldw;
     fa.ldw = ldw; fa.bias = bias; fa.y = y; fa.ldy = ldy; fa.colpart = colpart; fa.stat_shift = shift; fa.qt = qt;
     const int nwg = (int)((long)M * frames / qt);
     if (C == 64)
-        hipLaunchKernelGGL((kpconv_fused_kernel<64, 64>), dim3(nwg), dim3(512), 0, cofi_s(stream), fa);
+        hipLaunchKernelGGL((kpconv_fused_kernel<64, 64, REC>), dim3(nwg), dim3(512), 0, cofi_s(stream), fa);
     else
-        hipLaunchKernelGGL((kpconv_fused_kernel<32, 128>), dim3(nwg), dim3(512), 0, cofi_s(stream), fa);
+        hipLaunchKernelGGL((kpconv_fused_kernel<32, 128, REC>), dim3(nwg), dim3(512), 0, cofi_s(stream), fa);
     return cofi_launch_status();
+}
+
+extern "C" int cofi_kpconv_fused(const float *feats, int ldf, int N, int C, const float *q_pts, const float *s_pts, const int32_t *idx, int M, int H,
+                                 const float *kernel_points, float sigma, const uint8_t *row_pos, const void *w_planes, int ldw, const float *bias,
+                                 float *y, int ldy, float *colpart, int stat_width, int frames, const int32_t *order, cofi_stream_t stream) {
+    if (!feats || !q_pts || !s_pts || !idx || !kernel_points || !row_pos || !w_planes || !y) return COFI_EINVAL;
+    return kp_fused_launch<false>(feats, ldf, N, C, q_pts, s_pts, nullptr, idx, M, H, kernel_points, sigma, row_pos, w_planes, ldw, bias, y, ldy,
+                                  colpart, stat_width, frames, order, stream);
+}
+
+// cofi_kpconv_fused with the support as 16-byte records (see cofi_kpconv_aggregate_rec)
+extern "C" int cofi_kpconv_fused_rec(const float *feats, int ldf, int N, int C, const float *q_pts, const float *records, const int32_t *idx, int M,
+                                     int H, const float *kernel_points, float sigma, const void *w_planes, int ldw, const float *bias, float *y,
+                                     int ldy, float *colpart, int stat_width, int frames, const int32_t *order, cofi_stream_t stream) {
+    if (!feats || !q_pts || !records || !idx || !kernel_points || !w_planes || !y || ((uintptr_t)records & 15)) return COFI_EINVAL;
+    return kp_fused_launch<true>(feats, ldf, N, C, q_pts, nullptr, (const float4 *)records, idx, M, H, kernel_points, sigma, nullptr, w_planes, ldw,
+                                 bias, y, ldy, colpart, stat_width, frames, order, stream);
 }
 
 extern "C" int cofi_neighbor_maxpool(const float *x, int ldx, int N, int C, const int32_t *idx, int M, int H, float *out, int ldo,

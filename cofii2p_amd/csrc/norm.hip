@@ -159,22 +159,32 @@ struct GnApplyArgs {
     float slope;
     int groups;
     uint8_t *row_pos;   // optional: row_pos[m] = (sum_c y[m,c] > 0) (kpconv.py:113-114 for the next KPConv); needs C <= 256
+    const float *points;   // optional, with records: (M, 3) positions of the rows
+    float4 *records;       // optional, in place of row_pos: records[m] = (x, y, z, flag), flag = 1.0f where row_pos[m] would be 1 - the
+                           // 16-byte support record of the KPConv aggregation (cofi_kpconv_aggregate_rec)
 };
 
 // Row loop of the apply kernels for one float4 column chunk: a thread's rows are taken four at a time with every load issued
 // before the first use (x / res / y may alias as far as the compiler knows: written row by row it would serialise one memory
 // round trip per row).
+// PTS_EARLY: the positions of the records are requested with the row loads (4 more registers: the kernel of the hot path), else at the store.
+template <bool PTS_EARLY>
 __device__ __forceinline__ void gn_apply_rows(const GnApplyArgs &a, int c, const float (&sc)[4], const float (&sh)[4], const float (&rsc)[4],
                                               const float (&rsh)[4], int tr, int rpb, int tpr, int tc) {
     constexpr int RU = 4;
     const int stride = gridDim.x * rpb;
     for (int m0 = blockIdx.x * rpb + tr; m0 < a.M; m0 += RU * stride) {
         f32x4 xv[RU], rv[RU];
+        float pc[RU];   // PTS_EARLY: lane tc < 3 of a row loads coordinate tc of the row's position (host: tpr >= 4)
 #pragma unroll
         for (int u = 0; u < RU; ++u) {
             const int m = min(m0 + u * stride, a.M - 1);
             xv[u] = *reinterpret_cast<const f32x4 *>(a.x + (size_t)m * a.ldx + c);
             if (a.res) rv[u] = *reinterpret_cast<const f32x4 *>(a.res + (size_t)m * a.ldr + c);
+            if constexpr (PTS_EARLY) {
+                pc[u] = 0.f;
+                if (a.records && tc < 3) pc[u] = a.points[3 * (size_t)m + tc];
+            }
         }
 #pragma unroll
         for (int u = 0; u < RU; ++u) {
@@ -190,10 +200,20 @@ __device__ __forceinline__ void gn_apply_rows(const GnApplyArgs &a, int c, const
 #pragma unroll
                 for (int i = 0; i < 4; ++i) v[i] = v[i] >= 0.f ? v[i] : v[i] * a.slope;
                 *reinterpret_cast<float4 *>(a.y + (size_t)m * a.ldy + c) = make_float4(v[0], v[1], v[2], v[3]);
-                if (a.row_pos) {   // host guarantees tpr <= 64 and one column pass: the tpr lanes of a row are adjacent lanes of one wave
+                if (a.row_pos || a.records) {   // host guarantees tpr <= 64 and one column pass: the tpr lanes of a row are adjacent lanes of one wave
                     float rs = (v[0] + v[1]) + (v[2] + v[3]);
                     for (int o = 1; o < tpr; o <<= 1) rs += __shfl_xor(rs, o, 64);
-                    if (tc == 0) a.row_pos[m] = rs > 0.0f ? 1 : 0;
+                    if (a.records) {
+                        if constexpr (PTS_EARLY) {   // y and z come from the two lanes behind the row's first
+                            const float py = __shfl_down(pc[u], 1, 64), pz = __shfl_down(pc[u], 2, 64);
+                            if (tc == 0) a.records[m] = make_float4(pc[u], py, pz, rs > 0.0f ? 1.0f : 0.0f);
+                        } else if (tc == 0) {
+                            const float *p = a.points + 3 * (size_t)m;
+                            a.records[m] = make_float4(p[0], p[1], p[2], rs > 0.0f ? 1.0f : 0.0f);
+                        }
+                    } else if (tc == 0) {
+                        a.row_pos[m] = rs > 0.0f ? 1 : 0;
+                    }
                 }
             }
         }
@@ -216,6 +236,10 @@ __global__ __launch_bounds__(256) void group_norm_apply_kernel(GnApplyArgs a) {
         if (a.res) a.res += f * a.M * a.ldr;
         if (a.res_stats) a.res_stats += f * a.groups * 2;
         if (a.row_pos) a.row_pos += f * a.M;
+        if (a.records) {
+            a.points += f * a.M * 3;
+            a.records += f * a.M;
+        }
     }
     for (int cb = tc; cb < c4n; cb += tpr) {
         const int c = cb * 4;
@@ -235,7 +259,7 @@ __global__ __launch_bounds__(256) void group_norm_apply_kernel(GnApplyArgs a) {
                 rsh[i] = rb - rm * rr * rg;
             }
         }
-        gn_apply_rows(a, c, sc, sh, rsc, rsh, tr, rpb, tpr, tc);
+        gn_apply_rows<false>(a, c, sc, sh, rsc, rsh, tr, rpb, tpr, tc);
     }
 }
 
@@ -283,6 +307,10 @@ __global__ __launch_bounds__(256) void group_norm_apply_fused_kernel(GnFusedArgs
         fa.n.part += f * fa.n.nslab * fa.n.tcols * 2;
         if (fa.rn.part) fa.rn.part += f * fa.rn.nslab * fa.rn.tcols * 2;
         if (a.row_pos) a.row_pos += f * a.M;
+        if (a.records) {
+            a.points += f * a.M * 3;
+            a.records += f * a.M;
+        }
     }
     const float *nsc = fa.n.scsh ? fa.n.scsh + (size_t)blockIdx.y * 2 * a.C : nullptr;       // finalized scale | shift of this frame
     const float *rsc_g = fa.rn.scsh ? fa.rn.scsh + (size_t)blockIdx.y * 2 * a.C : nullptr;
@@ -316,7 +344,7 @@ __global__ __launch_bounds__(256) void group_norm_apply_fused_kernel(GnFusedArgs
                 }
             }
         }
-        gn_apply_rows(a, c, sc, sh, rsc, rsh, tr, rpb, tpr, tc);
+        gn_apply_rows<true>(a, c, sc, sh, rsc, rsh, tr, rpb, tpr, tc);
     }
 }
 
@@ -623,23 +651,42 @@ extern "C" int cofi_group_stats_exact(const float *x, int ldx, int M, int C, int
     return group_stats_entry(x, ldx, M, C, groups, eps, stats, ws, ws_bytes, frames, true, stream);
 }
 
-extern "C" int cofi_group_norm_apply(const float *x, int ldx, int M, int C, int groups, const float *stats, const float *gamma,
-                                     const float *beta, const float *res, int ldr, const float *res_stats,
-                                     const float *res_gamma, const float *res_beta, float slope, float *y, int ldy, uint8_t *row_pos,
-                                     int frames, cofi_stream_t stream) {
+static int group_norm_apply_entry(const float *x, int ldx, int M, int C, int groups, const float *stats, const float *gamma, const float *beta,
+                                  const float *res, int ldr, const float *res_stats, const float *res_gamma, const float *res_beta, float slope,
+                                  float *y, int ldy, uint8_t *row_pos, const float *points, float4 *records, int frames, cofi_stream_t stream) {
     if (!x || !stats || !y || M <= 0 || C <= 0 || groups <= 0 || (C % groups) || (C & 3) || (ldx & 3) || (ldy & 3)) return COFI_EINVAL;
     if ((gamma == nullptr) != (beta == nullptr) || (res_gamma == nullptr) != (res_beta == nullptr)) return COFI_EINVAL;
     if (res && (ldr & 3)) return COFI_EINVAL;
     if (frames <= 0 || (M % frames)) return COFI_EINVAL;
     const int Mf = M / frames;
-    GnApplyArgs a{x, stats, gamma, beta, res, res_stats, res_gamma, res_beta, y, ldx, ldr, ldy, Mf, C, C / groups, slope, groups, row_pos};
+    GnApplyArgs a{x, stats, gamma, beta, res, res_stats, res_gamma, res_beta, y, ldx, ldr, ldy, Mf, C, C / groups, slope, groups, row_pos, points, records};
     const int c4n = C >> 2, tpr = c4n < 256 ? c4n : 256, rpb = 256 / tpr;
-    if (row_pos && (tpr > 64 || (64 % tpr))) return COFI_EUNSUPPORTED;
+    if ((row_pos || records) && (tpr > 64 || (64 % tpr))) return COFI_EUNSUPPORTED;
+    if (records && tpr < 4) return COFI_EUNSUPPORTED;   // three lanes of a row carry its position
     int nb = cofi_cdiv(Mf, rpb * 4);  // ~4 rows per thread
     if (nb > 2048) nb = 2048;
     if (nb < 1) nb = 1;
     hipLaunchKernelGGL(group_norm_apply_kernel, dim3(nb, frames), dim3(256), 0, cofi_s(stream), a);
     return cofi_launch_status();
+}
+
+extern "C" int cofi_group_norm_apply(const float *x, int ldx, int M, int C, int groups, const float *stats, const float *gamma,
+                                     const float *beta, const float *res, int ldr, const float *res_stats,
+                                     const float *res_gamma, const float *res_beta, float slope, float *y, int ldy, uint8_t *row_pos,
+                                     int frames, cofi_stream_t stream) {
+    return group_norm_apply_entry(x, ldx, M, C, groups, stats, gamma, beta, res, ldr, res_stats, res_gamma, res_beta, slope, y, ldy, row_pos,
+                                  nullptr, nullptr, frames, stream);
+}
+
+// cofi_group_norm_apply that emits, in place of row_pos, the 16-byte support records (x, y, z, flag) of its rows for the KPConv
+// aggregation that consumes y (cofi_kpconv_aggregate_rec): points (M, 3), records (M, 4) floats, 16-byte aligned.
+extern "C" int cofi_group_norm_apply_rec(const float *x, int ldx, int M, int C, int groups, const float *stats, const float *gamma,
+                                         const float *beta, const float *res, int ldr, const float *res_stats, const float *res_gamma,
+                                         const float *res_beta, float slope, float *y, int ldy, const float *points, float *records, int frames,
+                                         cofi_stream_t stream) {
+    if (!points || !records || ((uintptr_t)records & 15)) return COFI_EINVAL;
+    return group_norm_apply_entry(x, ldx, M, C, groups, stats, gamma, beta, res, ldr, res_stats, res_gamma, res_beta, slope, y, ldy, nullptr,
+                                  points, (float4 *)records, frames, stream);
 }
 
 extern "C" int cofi_norm_finalize(const cofi_norm_desc_t *norm, int rows, int frames, float *scale_shift, cofi_stream_t stream) {
@@ -652,22 +699,23 @@ extern "C" int cofi_norm_finalize(const cofi_norm_desc_t *norm, int rows, int fr
     return cofi_launch_status();
 }
 
-extern "C" int cofi_group_norm_apply_partials(const float *x, int ldx, int M, int C, const cofi_norm_desc_t *norm, const float *res, int ldr,
-                                              const cofi_norm_desc_t *res_norm, float *y, int ldy, uint8_t *row_pos, int frames,
-                                              cofi_stream_t stream) {
+static int group_norm_apply_partials_entry(const float *x, int ldx, int M, int C, const cofi_norm_desc_t *norm, const float *res, int ldr,
+                                           const cofi_norm_desc_t *res_norm, float *y, int ldy, uint8_t *row_pos, const float *points,
+                                           float4 *records, int frames, cofi_stream_t stream) {
     if (!x || !norm || !y || M <= 0 || C <= 0 || (C & 3) || (ldx & 3) || (ldy & 3) || ldx < C || ldy < C) return COFI_EINVAL;
     if (res && ((ldr & 3) || ldr < C)) return COFI_EINVAL;
     if (frames <= 0 || (M % frames) || (res_norm && !res)) return COFI_EINVAL;
     if (norm->channels != C || (res_norm && res_norm->channels != C) || (res_norm && res_norm->groups != norm->groups)) return COFI_EINVAL;
     const int Mf = M / frames, c4n = C >> 2, tpr = c4n < 256 ? c4n : 256, rpb = 256 / tpr;
-    if (row_pos && (tpr > 64 || (64 % tpr))) return COFI_EUNSUPPORTED;
+    if ((row_pos || records) && (tpr > 64 || (64 % tpr))) return COFI_EUNSUPPORTED;
+    if (records && tpr < 4) return COFI_EUNSUPPORTED;   // three lanes of a row carry its position
     GnFusedArgs fa{};
     if (int rc = make_norm_src(norm, Mf, frames, 1 << 20, &fa.n)) return rc;
     if (res_norm)
         if (int rc = make_norm_src(res_norm, Mf, frames, 1 << 20, &fa.rn)) return rc;
     if (fa.n.groups > 1024) return COFI_EUNSUPPORTED;   // LDS statistics table
     fa.a = GnApplyArgs{x, nullptr, norm->gamma, norm->beta, res, nullptr, res_norm ? res_norm->gamma : nullptr, res_norm ? res_norm->beta : nullptr,
-                       y, ldx, ldr, ldy, Mf, C, C / norm->groups, norm->slope, norm->groups, row_pos};
+                       y, ldx, ldr, ldy, Mf, C, C / norm->groups, norm->slope, norm->groups, row_pos, points, records};
     int nb = cofi_cdiv(Mf, rpb * 4);
     constexpr int cap = 2048;   // workgroups per launch, grid-strided beyond (round-5 sweep of this cap: bandwidth-bound at every value)
     const int cap_f = cap / frames > 0 ? cap / frames : 1;
@@ -675,6 +723,20 @@ extern "C" int cofi_group_norm_apply_partials(const float *x, int ldx, int M, in
     if (nb < 1) nb = 1;
     hipLaunchKernelGGL(group_norm_apply_fused_kernel, dim3(nb, frames), dim3(256), 0, cofi_s(stream), fa);
     return cofi_launch_status();
+}
+
+extern "C" int cofi_group_norm_apply_partials(const float *x, int ldx, int M, int C, const cofi_norm_desc_t *norm, const float *res, int ldr,
+                                              const cofi_norm_desc_t *res_norm, float *y, int ldy, uint8_t *row_pos, int frames,
+                                              cofi_stream_t stream) {
+    return group_norm_apply_partials_entry(x, ldx, M, C, norm, res, ldr, res_norm, y, ldy, row_pos, nullptr, nullptr, frames, stream);
+}
+
+// cofi_group_norm_apply_partials that emits the support records in place of row_pos (see cofi_group_norm_apply_rec)
+extern "C" int cofi_group_norm_apply_partials_rec(const float *x, int ldx, int M, int C, const cofi_norm_desc_t *norm, const float *res, int ldr,
+                                                  const cofi_norm_desc_t *res_norm, float *y, int ldy, const float *points, float *records,
+                                                  int frames, cofi_stream_t stream) {
+    if (!points || !records || ((uintptr_t)records & 15)) return COFI_EINVAL;
+    return group_norm_apply_partials_entry(x, ldx, M, C, norm, res, ldr, res_norm, y, ldy, nullptr, points, (float4 *)records, frames, stream);
 }
 
 extern "C" int cofi_layer_norm(const float *x, int ldx, int M, int C, const float *gamma, const float *beta, float eps, int relu,

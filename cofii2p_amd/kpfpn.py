@@ -140,10 +140,10 @@ def _unary_raw(P, p: str, x, frames: int = 1):
     return y, _stats(y, part, frames, sw)
 
 
-def _unary(P, p: str, x, slope: float, out=None, frames: int = 1, want_row_pos: bool = False):
+def _unary(P, p: str, x, slope: float, out=None, frames: int = 1, want_row_pos: bool = False, points=None):
     y, st = _unary_raw(P, p, x, frames)
     return ops.group_norm_apply(y, st, P[p + "norm.norm.weight"], P[p + "norm.norm.bias"], slope=slope, out=out, frames=frames,
-                                want_row_pos=want_row_pos)
+                                want_row_pos=want_row_pos, points=points)
 
 
 def run_block(P, blk: KPBlock, feats, q_pts, s_pts, idx, out=None, concurrent: bool = True, frames: int = 1, order=None):
@@ -159,9 +159,10 @@ def run_block(P, blk: KPBlock, feats, q_pts, s_pts, idx, out=None, concurrent: b
         ys = sts = None
         if blk.has_shortcut_unary:
             ys, sts = _unary_raw(P, p + "unary_shortcut.", sc, frames)
-    # unary1 feeds the KPConv gather: its normalisation is materialised, and the apply kernel also emits the per-row flag
-    # the aggregation needs
-    x = _unary(P, p + "unary1.", feats, LRELU, frames=frames, want_row_pos=True) if blk.cin != blk.mid else feats
+    # unary1 feeds the KPConv gather: its normalisation is materialised, and the apply kernel also emits what the aggregation
+    # stages per support row: the 16-byte record (position, positive-sum flag); the rows of unary1 are the support points
+    # (a strided block: the finer stage's)
+    x = _unary(P, p + "unary1.", feats, LRELU, frames=frames, want_row_pos=True, points=s_pts) if blk.cin != blk.mid else feats
     y, st = _kpconv(P, p, x, q_pts, s_pts, idx, blk.sigma, frames, order)
     # norm_conv + LeakyReLU (modules.py:232-233) is consumed by unary2's Linear only: applied by that GEMM's operand loader
     x = ops.Normed(y, st, P[p + "norm_conv.norm.weight"], P[p + "norm_conv.norm.bias"], LRELU)

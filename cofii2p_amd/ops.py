@@ -538,6 +538,33 @@ def col_inv_norm_from_colpart(colpart, M: int, C: int, eps: float = 1e-12, frame
 
 
 # ------------------------------------------------------------------------------------------ KPConv
+# The aggregation kernels stage the support from ONE 16-byte record (x, y, z, flag) per row (cofi_kpconv_aggregate_rec): one gather per
+# neighbour instead of three position dwords and the flag byte.  Same kernels, same bits.  COFI_KPCONV_RECORDS=0: positions and
+# row_pos as separate arrays (A/B runs, tests).
+def kpconv_records() -> bool:
+    return os.environ.get("COFI_KPCONV_RECORDS", "1") != "0"
+
+
+def kp_pack_support(feats: torch.Tensor, points: torch.Tensor) -> torch.Tensor:
+    """-> records (N, 4) fp32 = (x, y, z, flag) per support row, flag = 1.0 where `row_sum_positive(feats)` is 1."""
+    lib = _lib.load()
+    _mat(feats, "feats")
+    N, C = feats.shape
+    if points.shape != (N, 3) or points.dtype != torch.float32 or not points.is_contiguous():
+        raise _lib.CofiError("kp_pack_support: points must be contiguous fp32 (N, 3)")
+    recs = torch.empty((N, 4), dtype=torch.float32, device=feats.device)
+    _lib.check(lib.cofi_kp_pack_support(_p(feats), _ld(feats), N, C, _p(points), _p(recs), _stream()), "cofi_kp_pack_support")
+    return recs
+
+
+def _support_records(feats, s_pts):
+    """The records the group_norm_apply that produced `feats` left on it (if they were built from these very points), else packed now."""
+    att = getattr(feats, "cofi_kp_records", None)
+    if att is not None and att[1] == s_pts.data_ptr() and att[0].shape[0] == s_pts.shape[0]:
+        return att[0]
+    return kp_pack_support(feats, s_pts)
+
+
 def row_sum_positive(feats: torch.Tensor) -> torch.Tensor:
     lib = _lib.load()
     _mat(feats, "feats")
@@ -573,6 +600,12 @@ def kpconv_aggregate(feats, q_pts, s_pts, idx, kernel_points, sigma: float, row_
                                           15 * C, _p(cnt), frames, _p(order), _stream())
         _lib.check(rc, "cofi_kpconv_aggregate_c4")
         return agg, cnt
+    if row_pos is None and kpconv_records():
+        recs = _support_records(feats, s_pts)
+        rc = lib.cofi_kpconv_aggregate_rec(_p(feats), _ld(feats), N // frames, C, _p(q_pts), _p(recs), _p(idx), M // frames, H, _p(kernel_points),
+                                           float(sigma), _p(agg), 15 * C, int(planes), _p(cnt), frames, _p(order), _stream())
+        _lib.check(rc, "cofi_kpconv_aggregate_rec")
+        return (SplitA(agg, 15 * C) if planes else agg), cnt
     if row_pos is None:
         row_pos = row_sum_positive(feats)
     rc = lib.cofi_kpconv_aggregate(_p(feats), _ld(feats), N // frames, C, _p(q_pts), _p(s_pts), _p(idx), M // frames, H,
@@ -607,10 +640,16 @@ def kpconv_fused(feats, q_pts, s_pts, idx, kernel_points, sigma: float, w: "Spli
         raise _lib.CofiError("kpconv_fused: shape not supported (C in {32, 64}, M % 16 == 0, bf16x3 arithmetic)")
     if row_pos is None:
         row_pos = getattr(feats, "cofi_row_pos", None)   # left there by the group_norm_apply that produced feats
-    if row_pos is None:
-        row_pos = row_sum_positive(feats)
     y = torch.empty((M, C), dtype=torch.float32, device=feats.device)
     part = torch.empty((M // sr, C // stat_width, 2), dtype=torch.float32, device=feats.device)
+    if row_pos is None and kpconv_records():
+        recs = _support_records(feats, s_pts)
+        rc = lib.cofi_kpconv_fused_rec(_p(feats), _ld(feats), N // frames, C, _p(q_pts), _p(recs), _p(idx), M // frames, H, _p(kernel_points),
+                                       float(sigma), _p(w.planes), w.ldp, _p(bias), _p(y), _ld(y), _p(part), stat_width, frames, _p(order), _stream())
+        _lib.check(rc, "cofi_kpconv_fused_rec")
+        return y, part, sr
+    if row_pos is None:
+        row_pos = row_sum_positive(feats)
     rc = lib.cofi_kpconv_fused(_p(feats), _ld(feats), N // frames, C, _p(q_pts), _p(s_pts), _p(idx), M // frames, H, _p(kernel_points), float(sigma),
                                _p(row_pos), _p(w.planes), w.ldp, _p(bias), _p(y), _ld(y), _p(part), stat_width, frames, _p(order), _stream())
     _lib.check(rc, "cofi_kpconv_fused")
@@ -662,23 +701,37 @@ def group_stats(x, groups: int, eps: float = 1e-5, frames: int = 1, exact: bool 
 
 
 def group_norm_apply(x, stats, gamma=None, beta=None, slope: float = 1.0, res=None, res_stats=None, res_gamma=None, res_beta=None,
-                     out=None, frames: int = 1, want_row_pos: bool = False):
+                     out=None, frames: int = 1, want_row_pos: bool = False, points=None):
     """stats: (groups,2) / stack mode (frames, groups, 2) tensor, or ColStats (statistics partials, folded in-kernel).
     want_row_pos (activation at most 256 wide): the kernel also emits row_pos = (row sum > 0), attached to the result as
-    `out.cofi_row_pos` for the KPConv that consumes it (kpconv.py:113-114)."""
+    `out.cofi_row_pos` for the KPConv that consumes it (kpconv.py:113-114).  With `points` (M, 3) - the positions of the rows - and the
+    records path on, the kernel writes the 16-byte support records (x, y, z, flag) instead, attached as `out.cofi_kp_records`."""
     lib = _lib.load()
     _mat(x, "x")
     M, C = x.shape
     if out is None:
         out = torch.empty((M, C), dtype=torch.float32, device=x.device)
+    for stale in ("cofi_row_pos", "cofi_kp_records"):   # a reused `out` must not carry what an earlier call attached
+        if hasattr(out, stale):
+            delattr(out, stale)
     c4n = C // 4
     row_pos = torch.empty((M,), dtype=torch.uint8, device=x.device) if (want_row_pos and C % 4 == 0 and c4n <= 64 and 64 % c4n == 0) else None
+    recs = None
+    if row_pos is not None and points is not None and c4n >= 4 and kpconv_records():
+        if points.shape != (M, 3) or points.dtype != torch.float32 or not points.is_contiguous():
+            raise _lib.CofiError("group_norm_apply: points must be contiguous fp32 (M, 3)")
+        row_pos, recs = None, torch.empty((M, 4), dtype=torch.float32, device=x.device)
     fused = isinstance(stats, ColStats) and stats.fusable() and (res_stats is None or (isinstance(res_stats, ColStats) and res_stats.fusable()))
     if fused:
         nd = stats.desc(gamma, beta, slope)
         rnd = None if res_stats is None else res_stats.desc(res_gamma, res_beta, 1.0)
-        rc = lib.cofi_group_norm_apply_partials(_p(x), _ld(x), M, C, ctypes.byref(nd), _p(res), 0 if res is None else _ld(res),
-                                                None if rnd is None else ctypes.byref(rnd), _p(out), _ld(out), _p(row_pos), frames, _stream())
+        if recs is not None:
+            rc = lib.cofi_group_norm_apply_partials_rec(_p(x), _ld(x), M, C, ctypes.byref(nd), _p(res), 0 if res is None else _ld(res),
+                                                        None if rnd is None else ctypes.byref(rnd), _p(out), _ld(out), _p(points), _p(recs), frames,
+                                                        _stream())
+        else:
+            rc = lib.cofi_group_norm_apply_partials(_p(x), _ld(x), M, C, ctypes.byref(nd), _p(res), 0 if res is None else _ld(res),
+                                                    None if rnd is None else ctypes.byref(rnd), _p(out), _ld(out), _p(row_pos), frames, _stream())
         _lib.check(rc, "cofi_group_norm_apply_partials")
     else:
         if isinstance(stats, ColStats):
@@ -686,12 +739,19 @@ def group_norm_apply(x, stats, gamma=None, beta=None, slope: float = 1.0, res=No
         if isinstance(res_stats, ColStats):
             res_stats = res_stats.finalize()
         groups = stats.shape[-2]
-        rc = lib.cofi_group_norm_apply(_p(x), _ld(x), M, C, groups, _p(stats), _p(gamma), _p(beta), _p(res), 0 if res is None else _ld(res),
-                                       _p(res_stats), _p(res_gamma), _p(res_beta), float(slope), _p(out), _ld(out), _p(row_pos), frames,
-                                       _stream())
+        if recs is not None:
+            rc = lib.cofi_group_norm_apply_rec(_p(x), _ld(x), M, C, groups, _p(stats), _p(gamma), _p(beta), _p(res), 0 if res is None else _ld(res),
+                                               _p(res_stats), _p(res_gamma), _p(res_beta), float(slope), _p(out), _ld(out), _p(points), _p(recs),
+                                               frames, _stream())
+        else:
+            rc = lib.cofi_group_norm_apply(_p(x), _ld(x), M, C, groups, _p(stats), _p(gamma), _p(beta), _p(res), 0 if res is None else _ld(res),
+                                           _p(res_stats), _p(res_gamma), _p(res_beta), float(slope), _p(out), _ld(out), _p(row_pos), frames,
+                                           _stream())
         _lib.check(rc, "cofi_group_norm_apply")
     if row_pos is not None:
         out.cofi_row_pos = row_pos
+    if recs is not None:
+        out.cofi_kp_records = (recs, points.data_ptr())   # valid for a KPConv over these very support points
     return out
 
 

@@ -185,6 +185,15 @@ int cofi_kpconv_aggregate(const float *feats, int ldf, int N, int C, const float
                           float *cnt, int frames, const int32_t *order /* optional (frames*M) frame-local
                           processing order of the queries, e.g. Morton-sorted: results do not depend on it */,
                           cofi_stream_t stream);
+/* The support as ONE 16-byte record per row, (frames * N, 4) floats = (x, y, z, flag), 16-byte aligned, flag = 1.0f where row_pos
+ * would be 1: the staging then costs one gather per neighbour instead of four.  The records come from the GroupNorm apply that
+ * produced feats (cofi_group_norm_apply_rec / _partials_rec) or, for any other feats, from cofi_kp_pack_support (N = all rows; the
+ * flag is cofi_row_sum_positive's).  cofi_kpconv_aggregate_rec = cofi_kpconv_aggregate with `records` in place of s_pts and row_pos:
+ * the same kernels, the same results. */
+int cofi_kp_pack_support(const float *feats, int ldf, int N, int C, const float *points /* (N,3) */, float *records, cofi_stream_t stream);
+int cofi_kpconv_aggregate_rec(const float *feats, int ldf, int N, int C, const float *q_pts, const float *records, const int32_t *idx,
+                              int M, int H, const float *kernel_points, float sigma, float *agg, int ld_agg, int agg_planes, float *cnt,
+                              int frames, const int32_t *order, cofi_stream_t stream);
 
 /* KPConv as ONE kernel for the narrow layers (C = 32 or 64 = in = out channels, the stages with the most queries):
  *   y[m] = (sum_k agg[m, k, :] W[k]) / max(#neighbours whose feature row sums to > 0, 1) + bias       (kpconv.py:91-116)
@@ -198,6 +207,10 @@ int cofi_kpconv_fused_slab_rows(int C, int M, int frames);
 int cofi_kpconv_fused(const float *feats, int ldf, int N, int C, const float *q_pts, const float *s_pts, const int32_t *idx, int M, int H,
                       const float *kernel_points, float sigma, const uint8_t *row_pos, const void *w_planes, int ldw, const float *bias,
                       float *y, int ldy, float *colpart, int stat_width, int frames, const int32_t *order, cofi_stream_t stream);
+/* cofi_kpconv_fused with the support as 16-byte records (see cofi_kpconv_aggregate_rec) in place of s_pts and row_pos */
+int cofi_kpconv_fused_rec(const float *feats, int ldf, int N, int C, const float *q_pts, const float *records, const int32_t *idx, int M, int H,
+                          const float *kernel_points, float sigma, const void *w_planes, int ldw, const float *bias, float *y, int ldy,
+                          float *colpart, int stat_width, int frames, const int32_t *order, cofi_stream_t stream);
 /* K3 / K4  neighbour max-pool and nearest up-sample.
  * Replace model/kpconv/functional.py:53-66 (`maxpool`) and :5-21 (`nearest_upsample`): a zero
  * pad row stands behind index N. */
@@ -306,6 +319,15 @@ int cofi_norm_finalize(const cofi_norm_desc_t *norm, int rows, int frames, float
 int cofi_group_norm_apply_partials(const float *x, int ldx, int M, int C, const cofi_norm_desc_t *norm, const float *res, int ldr,
                                    const cofi_norm_desc_t *res_norm, float *y, int ldy, uint8_t *row_pos, int frames,
                                    cofi_stream_t stream);
+/* The two apply entry points emitting, in place of row_pos, the 16-byte support record of every row for the KPConv aggregation that
+ * consumes y (cofi_kpconv_aggregate_rec): records[m] = (points[m], flag), flag = 1.0f where row_pos[m] would be 1.  points (M, 3),
+ * records (M, 4) floats, 16-byte aligned; 16 <= C <= 256.  No extra launch, no extra pass. */
+int cofi_group_norm_apply_rec(const float *x, int ldx, int M, int C, int groups, const float *stats, const float *gamma, const float *beta,
+                              const float *res, int ldr, const float *res_stats, const float *res_gamma, const float *res_beta, float slope,
+                              float *y, int ldy, const float *points, float *records, int frames, cofi_stream_t stream);
+int cofi_group_norm_apply_partials_rec(const float *x, int ldx, int M, int C, const cofi_norm_desc_t *norm, const float *res, int ldr,
+                                       const cofi_norm_desc_t *res_norm, float *y, int ldy, const float *points, float *records, int frames,
+                                       cofi_stream_t stream);
 
 /* Row LayerNorm: y = act(LN(x) * gamma + beta) (+ res).  Replaces nn.LayerNorm at
  * model/transformer/transformer.py:40-41,58,62 and model/network.py:29.  C <= 2048, C % 4 == 0. */
