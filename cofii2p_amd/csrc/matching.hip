@@ -151,6 +151,7 @@ struct FinishArgs {
     int N1, cap, ldf, C, H2, W2, ldxy, ldfpc, ldo;
     float cscale;
     int N4;   // stage-4 points per frame (stack mode: frame f = blockIdx.x / cap; every per-frame array advances by its own frame size)
+    int cameras;   // rig submissions (cofi_match_finish_rig): `cameras` consecutive frames share cloud f / cameras - pts4, pts1 and fpc hold frames / cameras blocks
 };
 constexpr int FIN_MAXC = 128;
 
@@ -160,8 +161,9 @@ __global__ __launch_bounds__(256) void match_finish_kernel(FinishArgs a) {
     const int f = blockIdx.x / a.cap, i = blockIdx.x - f * a.cap;
     a.count += 2 * f;
     if (i >= min(*a.count, a.cap)) return;
-    a.pts4 += (size_t)f * a.N4 * 3; a.pts1 += (size_t)f * a.N1 * 3; a.sel += (size_t)f * a.cap; a.xy += (size_t)f * 2 * a.ldxy;
-    a.fmap += (size_t)f * a.H2 * a.W2 * a.ldf; a.fpc += (size_t)f * a.N1 * a.ldfpc;
+    const int cl = f / a.cameras;   // the frame's cloud: the only per-cloud operands are pts4, pts1 and fpc
+    a.pts4 += (size_t)cl * a.N4 * 3; a.pts1 += (size_t)cl * a.N1 * 3; a.sel += (size_t)f * a.cap; a.xy += (size_t)f * 2 * a.ldxy;
+    a.fmap += (size_t)f * a.H2 * a.W2 * a.ldf; a.fpc += (size_t)cl * a.N1 * a.ldfpc;
     a.coarse_pts += (size_t)f * a.cap * 3; a.patches += (size_t)f * a.cap * a.C * 16; a.fine_pc += (size_t)f * a.cap * a.ldo;
     a.fine_xy += (size_t)f * 2 * a.cap; a.best += (size_t)f * a.cap;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -197,18 +199,27 @@ __global__ __launch_bounds__(256) void match_finish_kernel(FinishArgs a) {
 
 }  // namespace
 
+extern "C" int cofi_match_finish_rig(const float *pts4, const float *pts1, int N1, const int32_t *sel, const int32_t *count_dev, int cap,
+                                     const float *fmap, int ldf, int C, int H2, int W2, const float *coarse_xy, int ldxy, float center_scale,
+                                     const float *fine_pc_all, int ldfpc, float *coarse_pts, float *patches, float *fine_pc, int ldo,
+                                     float *fine_xy, int32_t *best, int N4, int frames, int cameras, cofi_stream_t stream) {
+    if (!pts4 || !pts1 || !sel || !count_dev || !fmap || !coarse_xy || !fine_pc_all || !coarse_pts || !patches || !fine_pc || !fine_xy || !best)
+        return COFI_EINVAL;
+    if (N1 <= 0 || cap <= 0 || C <= 0 || H2 <= 0 || W2 <= 0 || ldf < C || ldfpc < C || ldo < C || N4 <= 0 || frames <= 0) return COFI_EINVAL;
+    if (cameras <= 0 || frames % cameras) return COFI_EINVAL;
+    if (C > FIN_MAXC) return COFI_EUNSUPPORTED;
+    FinishArgs a{pts4, pts1, fmap, coarse_xy, fine_pc_all, sel, count_dev, coarse_pts, patches, fine_pc, fine_xy, best,
+                 N1, cap, ldf, C, H2, W2, ldxy, ldfpc, ldo, center_scale, N4, cameras};
+    hipLaunchKernelGGL(match_finish_kernel, dim3(cap * frames), dim3(256), 0, cofi_s(stream), a);
+    return cofi_launch_status();
+}
+
 extern "C" int cofi_match_finish(const float *pts4, const float *pts1, int N1, const int32_t *sel, const int32_t *count_dev, int cap,
                                  const float *fmap, int ldf, int C, int H2, int W2, const float *coarse_xy, int ldxy, float center_scale,
                                  const float *fine_pc_all, int ldfpc, float *coarse_pts, float *patches, float *fine_pc, int ldo,
                                  float *fine_xy, int32_t *best, int N4, int frames, cofi_stream_t stream) {
-    if (!pts4 || !pts1 || !sel || !count_dev || !fmap || !coarse_xy || !fine_pc_all || !coarse_pts || !patches || !fine_pc || !fine_xy || !best)
-        return COFI_EINVAL;
-    if (N1 <= 0 || cap <= 0 || C <= 0 || H2 <= 0 || W2 <= 0 || ldf < C || ldfpc < C || ldo < C || N4 <= 0 || frames <= 0) return COFI_EINVAL;
-    if (C > FIN_MAXC) return COFI_EUNSUPPORTED;
-    FinishArgs a{pts4, pts1, fmap, coarse_xy, fine_pc_all, sel, count_dev, coarse_pts, patches, fine_pc, fine_xy, best,
-                 N1, cap, ldf, C, H2, W2, ldxy, ldfpc, ldo, center_scale, N4};
-    hipLaunchKernelGGL(match_finish_kernel, dim3(cap * frames), dim3(256), 0, cofi_s(stream), a);
-    return cofi_launch_status();
+    return cofi_match_finish_rig(pts4, pts1, N1, sel, count_dev, cap, fmap, ldf, C, H2, W2, coarse_xy, ldxy, center_scale, fine_pc_all, ldfpc,
+                                 coarse_pts, patches, fine_pc, ldo, fine_xy, best, N4, frames, 1, stream);
 }
 
 extern "C" int cofi_row_argmin_1m(const float *sim, int lds, int N, int P, int32_t *pix, cofi_stream_t stream) {

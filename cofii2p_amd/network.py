@@ -209,7 +209,7 @@ class CoFiI2P(nn.Module):
 
     # ------------------------------------------------------------------ device-side forward (no host sync)
     def _run_device(self, P, points, neighbors, subsampling, upsampling, feats, img, mode, fine_center_kpt_coors,
-                    fine_pc_inline_index, taps=None, order=None, pc_first: bool = False):
+                    fine_pc_inline_index, taps=None, order=None, pc_first: bool = False, cameras: int = 1):
         """Everything of network.py:74-161 that runs on the device.  Test-mode outputs are sized at
         capacity (N4 rows) with the match count left in device memory: capturable in a hipGraph.
 
@@ -217,9 +217,20 @@ class CoFiI2P(nn.Module):
         its rows (index tables frame-local).  All per-frame statistics (GroupNorm, InstanceNorm, the token-axis
         Q normalisation), the neighbour gathers, attention and the matching are computed per frame inside the
         same launches; row-wise kernels (GEMMs, LayerNorm, ...) just see B times more rows.  Outputs are lists
-        with one entry per frame."""
+        with one entry per frame.
+
+        RIG (cameras = C > 1, mode='test'): the B images are those of S = B // C clouds, image f looking at cloud f // C.  The point-side
+        tensors hold S frames; the KPConv-FPN, the point MLP and the position encoding run once per cloud and the coarse point tokens are
+        copied C times into the transformer's point stream (ops.repeat_frames).  From there on everything is per image, as in stack
+        mode; the matching tail reads the points and fine descriptors of cloud f // C.  Outputs: B per-image records, laid out as a
+        stack-mode submission of B frames lays them out."""
         dev = img.device
         B = img.shape[0]
+        if cameras != 1 and (mode != "test" or taps is not None):
+            raise ValueError("a rig (cameras = %d > 1) serves mode='test' only (forward_async): mode=%r shares no cloud between images" % (cameras, mode))
+        if cameras < 1 or B % cameras:
+            raise _lib.CofiError("cameras = %d does not divide the B = %d images of the submission" % (cameras, B))
+        S = B // cameras   # clouds
         if mode not in ("test", "val") and B != 1:
             raise ValueError("stack mode (B > 1) serves mode='test' and mode='val'")
         # mode='val' with labels of a whole submission - fine_center_kpt_coors (B, 2, K), fine_pc_inline_index (B, K), int64 / int32 device
@@ -227,7 +238,7 @@ class CoFiI2P(nn.Module):
         val_batched = mode == "val" and fine_center_kpt_coors is not None and fine_center_kpt_coors.dim() == 3
         if B != 1 and mode == "val" and not val_batched:
             raise ValueError("stack mode (B > 1) in mode='val' needs labels of shape (B, 2, K) / (B, K): forward_val_async")
-        N4 = points[-1].shape[0] // B
+        N4 = points[-1].shape[0] // S   # per cloud
         H8, W8 = img.shape[2] // 8, img.shape[3] // 8
         T_img, C = H8 * W8, D_MODEL
         ts = transformer.TokenStreams(B * T_img, B * N4, D_MODEL, dev)
@@ -247,10 +258,14 @@ class CoFiI2P(nn.Module):
 
         def point_branch():   # network.py:76,83-84,107,111
             # F.normalize of the fine point descriptors (network.py:83) rides in decoder2's GEMM epilogue (taps: the raw decoder output is wanted)
-            pc_set_ = kpfpn.run_fpn(P, points, neighbors, subsampling, upsampling, feats, taps=taps, frames=B, order=order, l2norm_fine=taps is None)
-            fine_pc_ = pc_set_[0] if taps is None else ops.l2norm_rows(pc_set_[0])  # (B*N1,64)
-            self._pc_feature_mlp(P, pc_set_[-1], out=ts.pc[0][:, :D_MODEL], l2norm=True)   # ... and of the coarse tokens (network.py:84) in the MLP's last GEMM
-            ops.pos_sine(points[-1], ts.pc[0], accumulate=True)
+            pc_set_ = kpfpn.run_fpn(P, points, neighbors, subsampling, upsampling, feats, taps=taps, frames=S, order=order, l2norm_fine=taps is None)
+            fine_pc_ = pc_set_[0] if taps is None else ops.l2norm_rows(pc_set_[0])  # (S*N1,64)
+            # a rig: the tokens of the S clouds are made once, then copied in front of each of the cloud's cameras
+            tok = ts.pc[0] if cameras == 1 else torch.empty((S * N4, D_MODEL), dtype=torch.float32, device=dev)
+            self._pc_feature_mlp(P, pc_set_[-1], out=tok[:, :D_MODEL], l2norm=True)   # ... and of the coarse tokens (network.py:84) in the MLP's last GEMM
+            ops.pos_sine(points[-1], tok, accumulate=True)
+            if cameras != 1:
+                ops.repeat_frames(tok, ts.pc[0][:, :D_MODEL], S, cameras)
             return pc_set_, fine_pc_
 
         # The two encoders are independent.  In a LINEAR capture (forward_async) their order is free: odd slots run the point encoder
@@ -292,7 +307,7 @@ class CoFiI2P(nn.Module):
         br_up.join(up2)
         if taps is not None:
             taps.update(up2=up2, fine_pc=fine_pc, tok_img_out=tok_img, tok_pc_out=tok_pc)
-        N1 = points[1].shape[0] // B
+        N1 = points[1].shape[0] // S   # per cloud
         P2 = H2 * W2
         # ---- per-frame output layouts + matching: one launch each for all B frames (network.py:145-161; the count stays on the device)
         if img_desc_t is None:   # B > 1 (or no fused chain): channel-major descriptor outputs of every frame
@@ -309,7 +324,7 @@ class CoFiI2P(nn.Module):
             sel, xy, cnt = sel.reshape(B, N4), xy.reshape(B, 2, N4), cnt.reshape(B, 2)
             if C2 <= 128:   # coarse point, point2node, patch, fine descriptor and the caller's fine matching (eval_all.py:99-105): one launch
                 cpts, pat, fpcs, fxy, fbest = (t if B > 1 else t[None] for t in
-                                               ops.match_finish(points[-1], points[1], sel, cnt, up2, H2, W2, xy, fine_pc, 4.0, frames=B))
+                                               ops.match_finish(points[-1], points[1], sel, cnt, up2, H2, W2, xy, fine_pc, 4.0, frames=B, cameras=cameras))
         if val_batched:   # network.py:137-141 for all frames: one launch (cofi_val_gather), labels read in place
             K = fine_center_kpt_coors.shape[2]
             if tuple(fine_center_kpt_coors.shape) != (B, 2, K) or tuple(fine_pc_inline_index.shape) != (B, K):
@@ -319,7 +334,8 @@ class CoFiI2P(nn.Module):
         for f in range(B):  # per-frame views
             o = {"img_desc": img_t[f].reshape(1, C, H8, W8), "pc_desc": pc_t[f],
                  "img_score": img_score[f * T_img:(f + 1) * T_img].reshape(1, 1, H8, W8), "pc_score": pc_score[f * N4:(f + 1) * N4].reshape(1, 1, N4)}
-            fpc = fine_pc[f * N1:(f + 1) * N1]
+            cl = f // cameras   # the frame's cloud
+            fpc = fine_pc[cl * N1:(cl + 1) * N1]
             up2_f = up2[f * P2:(f + 1) * P2]
             if val_batched:
                 o["patches"], o["fine_pc"] = pat_all[f].reshape(K, C2, 4, 4), fpc_all[f]
@@ -335,7 +351,7 @@ class CoFiI2P(nn.Module):
                 if C2 <= 128:
                     o["coarse_pts"], o["patches"], o["fine_pc"], o["fine_xy"], o["fine_best"] = cpts[f], pat[f], fpcs[f], fxy[f], fbest[f]
                 else:
-                    pts4, pts1 = points[-1][f * N4:(f + 1) * N4], points[1][f * N1:(f + 1) * N1]
+                    pts4, pts1 = points[-1][cl * N4:(cl + 1) * N4], points[1][cl * N1:(cl + 1) * N1]
                     o["coarse_pts"] = ops.gather_points_sel(pts4, sel[f], cnt[f])
                     node = ops.nearest_node_sel(pts1, pts4, sel[f], cnt[f])
                     o["patches"] = ops.extract_patches_nhwc(up2_f, H2, W2, xy[f], cnt[f], N4, 4.0)
@@ -367,7 +383,7 @@ class CoFiI2P(nn.Module):
         return self
 
     def _graph_forward(self, P, points, neighbors, subsampling, upsampling, feats, img, mode, kpt, inl, slot: int = 0,
-                       branch_mask: int = 7, order=None, inputs_stable: bool = False):
+                       branch_mask: int = 7, order=None, inputs_stable: bool = False, cameras: int = 1):
         def sig(t):
             if t is None:
                 return None
@@ -381,7 +397,7 @@ class CoFiI2P(nn.Module):
         tensors = list(points) + list(neighbors) + list(subsampling) + list(upsampling) + order + [feats, img, kpt, inl]
         # everything a captured launch sequence depends on besides the tensor signature: arithmetic, optional branches
         key = ("stable" if inputs_stable else "copy", mode, str(img.device), slot, branch_mask, ops.gemm_mode(), ops.f16x3_big(), self.compute_unused_image_maps,
-               transformer.JOINT_SELF, transformer.FUSED_CHAIN, transformer.TAIL_MAX_ROWS, kpfpn.FUSED_KPCONV, kpfpn.AGG_PLANES) + tuple(sig(t) for t in tensors)
+               transformer.JOINT_SELF, transformer.FUSED_CHAIN, transformer.TAIL_MAX_ROWS, kpfpn.FUSED_KPCONV, kpfpn.AGG_PLANES, cameras) + tuple(sig(t) for t in tensors)
         saved_mask, saved_slot = ops.BRANCH_MASK, ops.Workspace.slot
         ops.set_workspace_slot(slot)
         ops.BRANCH_MASK = branch_mask  # which intra-frame forks the capture records
@@ -406,7 +422,7 @@ class CoFiI2P(nn.Module):
                 o = [0, n[0], n[0] + n[1], n[0] + n[1] + n[2], n[0] + n[1] + n[2] + n[3], sum(n)]
                 args = (static[o[0]:o[1]], static[o[1]:o[2]], static[o[2]:o[3]], static[o[3]:o[4]], static[o[5]], static[o[5] + 1], mode,
                         static[o[5] + 2], static[o[5] + 3], None, (static[o[4]:o[5]] or None),
-                        ALTERNATE_ORDER and branch_mask == 0 and bool(slot & 1))
+                        ALTERNATE_ORDER and branch_mask == 0 and bool(slot & 1), cameras)
                 # warm-up AND capture run on one persistent stream, so every per-stream workspace is grown (in the
                 # ordinary allocator pool) before the capture starts and nothing is allocated for it inside
                 if getattr(self, "_capture_stream", None) is None or self._capture_stream.device != img.device:
@@ -440,7 +456,9 @@ class CoFiI2P(nn.Module):
     @staticmethod
     def stack_frames(pyramids, imgs):
         """B single-frame inputs -> one stack-mode input: every tensor concatenated along its rows (index tables stay
-        frame-local, int32), images stacked to (B,3,H,W).  All frames must have identical sizes."""
+        frame-local, int32), images stacked to (B,3,H,W).  All frames must have identical sizes.  The two lists need not be equally
+        long: S pyramids and B = S * C images (the C images of cloud 0 first, then those of cloud 1, ...) are the input of a rig
+        submission, `forward_async(slot, stacked, imgs, cameras=C)`."""
         out = {}
         for k in ("points", "neighbors", "subsampling", "upsampling"):
             out[k] = [torch.cat([CoFiI2P._as_idx32(p[k][i]) if k != "points" else p[k][i] for p in pyramids], 0).contiguous()
@@ -474,7 +492,7 @@ class CoFiI2P(nn.Module):
 
     @torch.no_grad()
     def forward_async(self, slot: int, pc_data_dict, img, mode: str = "test", inputs_stable: bool = False, pose_K=None,
-                      pose_iterations: int = 10000, pose_seed: int = 0, eval_into=None):
+                      pose_iterations: int = 10000, pose_seed: int = 0, eval_into=None, cameras: int = 1):
         """Enqueue one test-mode forward on the CURRENT stream through the hipGraph of slot `slot` and return
         immediately (no host sync).  `img` (1,3,H,W) = one frame, or (B,3,H,W) with a stack-mode `pc_data_dict`
         (see stack_frames) = B frames through the same launches.  Slots own their static buffers and scratch, so
@@ -498,10 +516,20 @@ class CoFiI2P(nn.Module):
         are enqueued behind the pose tail, before the handle's `done` event: frame f writes row row_index[f] of `table`
         (evaluation.EvalTable), a negative index nothing.  P_gt (B,4,4) float64 or float32 and row_index (B,) int32 are contiguous device
         tensors read in place (keep them unmodified until `finish()`).  With the default None nothing about the call, its handle or its
-        captured graphs changes."""
+        captured graphs changes.
+
+        cameras = C > 1: a RIG submission - the B images are those of S = B // C clouds, C consecutive images per cloud (image f looks at
+        cloud f // C: six cameras around one sweep, a stereo pair, several images against one sub-map).  `pc_data_dict` holds the S
+        clouds in stack-mode layout (`stack_frames(S pyramids, B images)` builds exactly this input; preprocess.FrameStack(cameras=C)
+        fills it in place), and the point encoder runs once per cloud instead of once per image.  Outputs, handle, pose tail (pose_K
+        (B,3,3)) and eval_into are those of a stack-mode submission of B frames.  Refused before anything is enqueued: a C that does not
+        divide B, point-side rows that S does not divide."""
         if mode != "test":
+            if cameras != 1:
+                raise ValueError("a rig (cameras = %d > 1) serves mode='test' only, got mode=%r" % (cameras, mode))
             raise ValueError("forward_async serves the test-mode pipeline")
         _lib.load()
+        self._check_rig(pc_data_dict, img, cameras)
         if eval_into is not None:
             from . import evaluation
 
@@ -509,7 +537,25 @@ class CoFiI2P(nn.Module):
                 raise _lib.CofiError("forward_async(eval_into=...): the monitors read the submission's poses - pass pose_K")
             evaluation.check_eval_into(eval_into, img.shape[0] if img.dim() == 4 else 1, img.device)
         with ops.arithmetic(self.arithmetic):
-            return self._forward_async(slot, pc_data_dict, img, mode, inputs_stable, pose_K, pose_iterations, pose_seed, eval_into)
+            return self._forward_async(slot, pc_data_dict, img, mode, inputs_stable, pose_K, pose_iterations, pose_seed, eval_into, cameras)
+
+    @staticmethod
+    def _check_rig(pc_data_dict, img, cameras):
+        """the shape rules of a rig submission (cameras > 1), checked before anything is enqueued"""
+        if not isinstance(cameras, int) or cameras < 1:
+            raise _lib.CofiError("forward_async: cameras must be an integer >= 1, got %r" % (cameras,))
+        if cameras == 1:
+            return
+        B = img.shape[0] if img.dim() == 4 else 1
+        if B % cameras:
+            raise _lib.CofiError("forward_async: B = %d images are no whole number of rigs of C = %d cameras" % (B, cameras))
+        S = B // cameras
+        named = [("%s[%d]" % (k, i), t) for k in ("points", "neighbors", "subsampling", "upsampling") for i, t in enumerate(pc_data_dict[k])]
+        named += [("order[%d]" % i, t) for i, t in enumerate(pc_data_dict.get("order") or [])] + [("feats", pc_data_dict["feats"])]
+        for name, t in named:
+            if t.shape[0] % S:
+                raise _lib.CofiError("forward_async: B = %d images with C = %d cameras are S = %d clouds, which does not divide the %d rows of %s"
+                                     % (B, cameras, S, t.shape[0], name))
 
     def _enqueue_pose(self, slot, outs, K, iterations, seed):
         """the batched pose tail of a submission, on the current stream, into buffers the slot owns"""
@@ -540,7 +586,8 @@ class CoFiI2P(nn.Module):
                                                             iterations=iterations, seed=seed, coord_major=True)
         return {"result": res, "R": R, "t": t, "inliers": mask}, K
 
-    def _forward_async(self, slot, pc_data_dict, img, mode, inputs_stable, pose_K=None, pose_iterations=10000, pose_seed=0, eval_into=None):
+    def _forward_async(self, slot, pc_data_dict, img, mode, inputs_stable, pose_K=None, pose_iterations=10000, pose_seed=0, eval_into=None,
+                       cameras=1):
         P = self._pack(img.device)
         if inputs_stable:
             for k in ("points", "neighbors", "subsampling", "upsampling"):
@@ -555,7 +602,7 @@ class CoFiI2P(nn.Module):
         # fork/join only adds join latency then — measured 254 vs 331 frames/s at two frames in flight)
         outs = self._graph_forward(P, points, tabs[0], tabs[1], tabs[2], pc_data_dict["feats"].contiguous(), img.contiguous(), mode, None,
                                    None, slot=slot, branch_mask=self.async_branch_mask,
-                                   order=pc_data_dict.get("order"), inputs_stable=inputs_stable)
+                                   order=pc_data_dict.get("order"), inputs_stable=inputs_stable, cameras=cameras)
         hosts = self.__dict__.setdefault("_count_host", {})   # one pinned landing buffer per slot (a slot is finished before it is reused)
         host = hosts.get((slot, len(outs)))
         if host is None:
@@ -574,7 +621,8 @@ class CoFiI2P(nn.Module):
         return handle
 
     @torch.no_grad()
-    def forward_val_async(self, slot: int, pc_data_dict, img, fine_center_kpt_coors, fine_pc_inline_index, inputs_stable: bool = False):
+    def forward_val_async(self, slot: int, pc_data_dict, img, fine_center_kpt_coors, fine_pc_inline_index, inputs_stable: bool = False,
+                          cameras: int = 1):
         """The validation pass's forward (train.py:68-70: model.eval(), mode='val') for B frames as ONE stack-mode submission on the
         current stream, through the hipGraph of slot `slot` (per slot and input signature; the labels are part of the staged inputs).
         `img` (B,3,H,W) with a stack-mode `pc_data_dict` (see stack_frames); fine_center_kpt_coors (B, 2, K) and fine_pc_inline_index
@@ -583,7 +631,11 @@ class CoFiI2P(nn.Module):
         handle["out"][0] also the submission-wide tensors validation.val_monitors reads in place (patches_all (B, K, C2, 16), fine_pc_all
         (B, K, C2), ...); `finish_val(handle)` synchronises on this submission and returns the reference's tuples.  Slots, their reuse and
         inputs_stable are those of forward_async.  Inference only: a module in train() mode is refused (batch statistics belong to
-        forward(mode='val') there), and mode='train' keeps refusing B > 1."""
+        forward(mode='val') there), and mode='train' keeps refusing B > 1.  cameras: accepted to be refused - a rig (cameras > 1) is served
+        by forward_async(mode='test') only."""
+        if cameras != 1:
+            raise ValueError("forward_val_async: a rig (cameras = %r) is served by forward_async(mode='test') only; validation labels are per "
+                             "(cloud, image) pair - repeat the cloud per image" % (cameras,))
         if self.training:
             raise ValueError("forward_val_async is the eval()-mode validation pass (train.py:37): call model.eval() first")
         _lib.load()
@@ -655,7 +707,7 @@ class CoFiI2P(nn.Module):
         self.last_match_frames = per_frame   # stack mode: one last_match record per frame
         return res[0] if len(res) == 1 else res
 
-    def forward(self, pc_data_dict, img, fine_center_kpt_coors, fine_xy, fine_pc_inline_index, mode, taps=None):
+    def forward(self, pc_data_dict, img, fine_center_kpt_coors, fine_xy, fine_pc_inline_index, mode, taps=None, cameras: int = 1):
         """model/network.py:74-164.  ``fine_xy`` is unused (as in the reference).
 
         TRAINING (train.py:224-226 followed by loss.backward(), train.py:285): mode='train' with autograd enabled - or mode 'train' /
@@ -666,7 +718,10 @@ class CoFiI2P(nn.Module):
         INFERENCE: everything else - evaluation/eval_all.py, train.py's validation pass (test_acc, train.py:27-70: model.eval() and
         mode='val', with autograd still enabled there - nothing requires grad, so it lands here) - runs the fused, folded kernel sequence (optionally a hipGraph) and returns tensors without a
         graph.  mode='test' is never differentiable (its match selection is a host-visible count, network.py:145-151): inputs that
-        require grad are refused there instead of silently losing their gradient."""
+        require grad are refused there instead of silently losing their gradient.  cameras: accepted to be refused - a rig (one cloud under
+        several images) is a forward_async submission."""
+        if cameras != 1:
+            raise ValueError("forward() evaluates one (cloud, image) pair per call: a rig (cameras = %r) is served by forward_async(..., cameras=C)" % (cameras,))
         if mode in ("train", "val") and (self.training or (mode == "train" and torch.is_grad_enabled())
                                          or (torch.is_grad_enabled() and (img.requires_grad or pc_data_dict["feats"].requires_grad))):
             from . import train_forward

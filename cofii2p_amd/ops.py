@@ -1164,6 +1164,22 @@ class MultiCopy:
         _lib.check(lib.cofi_multi_copy(_p(table), len(pairs), MULTI_COPY_BLOCKS, _stream()), "cofi_multi_copy")
 
 
+def repeat_frames(src, dst, frames: int, times: int):
+    """dst[(s * times + c) * n + r] = src[s * n + r] for the `frames` blocks of n = src.shape[0] // frames rows of src, c < times
+    (cofi_repeat_frames): torch.repeat_interleave of row blocks into an existing buffer.  src (frames * n, cols) and dst
+    (frames * times * n, cols) are row-major views with any leading dimension (dst: a column slice of a wider buffer whose other columns
+    are left alone)."""
+    lib = _lib.load()
+    _mat(src, "src"), _mat(dst, "dst")
+    if frames < 1 or times < 1 or src.shape[0] % frames or dst.shape[0] != src.shape[0] * times or dst.shape[1] != src.shape[1]:
+        raise _lib.CofiError("repeat_frames: src %s in %d blocks repeated %d times does not fill dst %s" % (tuple(src.shape), frames, times, tuple(dst.shape)))
+    if src.numel() == 0:
+        return dst
+    _lib.check(lib.cofi_repeat_frames(_p(src), _ld(src), src.shape[0] // frames, src.shape[1], frames, times, _p(dst), _ld(dst), _stream()),
+               "cofi_repeat_frames")
+    return dst
+
+
 # ------------------------------------------------------------------------------------------ KNN / indices
 KNN_GRID_MIN_SUPPORT = 1024   # smaller support sets: brute force
 
@@ -1337,15 +1353,21 @@ def fine_match(patches, pc_feats, xy, cnt, center_scale: float):
     return fine_xy, best
 
 
-def match_finish(pts4, pts1, sel, cnt, fmap, H2: int, W2: int, xy, fine_pc_all, center_scale: float, frames: int = 1):
+def match_finish(pts4, pts1, sel, cnt, fmap, H2: int, W2: int, xy, fine_pc_all, center_scale: float, frames: int = 1, cameras: int = 1):
     """The tail of a test-mode forward in one launch (cofi_match_finish): -> coarse_pts (cap,3), patches (cap,C,16), fine_pc (cap,C),
     fine_xy (2,cap), best (cap,) - the outputs of gather_points_sel + nearest_node_sel + gather_rows_sel + extract_patches_nhwc +
     fine_match, bit for bit: the kernels share their device bodies (csrc/match_parts.h).  frames > 1 (stack mode: every input holds `frames` equally sized blocks; sel (frames, cap), xy (frames, 2, cap), cnt (frames, 2)):
-    the outputs gain a leading frame axis."""
+    the outputs gain a leading frame axis.  cameras > 1 (a rig, cofi_match_finish_rig): image f looks at cloud f // cameras, and pts4,
+    pts1 and fine_pc_all - the operands that belong to the cloud - hold frames // cameras blocks; everything else stays per image."""
     lib = _lib.load()
     _mat(fmap, "fmap"), _mat(fine_pc_all, "fine_pc_all")
-    if sel.numel() % frames or pts4.shape[0] % frames or pts1.shape[0] % frames or fmap.shape[0] != frames * H2 * W2 or not (sel.is_contiguous() and xy.is_contiguous()):
+    if cameras < 1 or frames % cameras:
+        raise _lib.CofiError("match_finish: %d frames are no whole number of rigs of %d cameras" % (frames, cameras))
+    clouds = frames // cameras
+    if sel.numel() % frames or pts4.shape[0] % clouds or pts1.shape[0] % clouds or fmap.shape[0] != frames * H2 * W2 or not (sel.is_contiguous() and xy.is_contiguous()):
         raise _lib.CofiError("match_finish: shape mismatch")
+    if cameras > 1 and (fine_pc_all.shape[0] != pts1.shape[0] or cnt.numel() != 2 * frames or xy.numel() < 2 * sel.numel()):
+        raise _lib.CofiError("match_finish: a rig of %d cameras needs fine_pc_all and pts1 of %d clouds, cnt (frames, 2) and xy (frames, 2, cap)" % (cameras, clouds))
     cap, C, dev = sel.numel() // frames, fmap.shape[1], fmap.device
     lead = () if frames == 1 else (frames,)
     coarse_pts = torch.empty(lead + (cap, 3), dtype=torch.float32, device=dev)
@@ -1353,10 +1375,13 @@ def match_finish(pts4, pts1, sel, cnt, fmap, H2: int, W2: int, xy, fine_pc_all, 
     fine_pc = torch.empty(lead + (cap, C), dtype=torch.float32, device=dev)
     fine_xy = torch.empty(lead + (2, cap), dtype=torch.float32, device=dev)
     best = torch.empty(lead + (cap,), dtype=torch.int32, device=dev)
-    rc = lib.cofi_match_finish(_p(pts4.contiguous()), _p(pts1.contiguous()), pts1.shape[0] // frames, _p(sel), _p(cnt), cap, _p(fmap), _ld(fmap), C, H2, W2,
-                               _p(xy), xy.stride(-2), float(center_scale), _p(fine_pc_all), _ld(fine_pc_all), _p(coarse_pts), _p(patches), _p(fine_pc),
-                               C, _p(fine_xy), _p(best), pts4.shape[0] // frames, frames, _stream())
-    _lib.check(rc, "cofi_match_finish")
+    args = (_p(pts4.contiguous()), _p(pts1.contiguous()), pts1.shape[0] // clouds, _p(sel), _p(cnt), cap, _p(fmap), _ld(fmap), C, H2, W2,
+            _p(xy), xy.stride(-2), float(center_scale), _p(fine_pc_all), _ld(fine_pc_all), _p(coarse_pts), _p(patches), _p(fine_pc),
+            C, _p(fine_xy), _p(best), pts4.shape[0] // clouds, frames)
+    if cameras == 1:
+        _lib.check(lib.cofi_match_finish(*args, _stream()), "cofi_match_finish")
+    else:
+        _lib.check(lib.cofi_match_finish_rig(*args, cameras, _stream()), "cofi_match_finish_rig")
     return coarse_pts, patches, fine_pc, fine_xy, best
 
 

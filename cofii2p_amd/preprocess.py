@@ -107,21 +107,51 @@ class FrameStack:
     frame-local int32, images (B, 3, H, W)) that a loader fills FRAME BY FRAME: `put(f, pyramid, feats, img)` writes frame f's tensors
     into their row blocks with ONE batched copy launch (27 MB for a KITTI frame, ~10 us), so per-frame producers (PyramidGraph, FrameLoader
     slots) can feed `forward_async(slot, stack.pyr, stack.img, inputs_stable=True)` submissions of B frames without a gather pass or a
-    host synchronisation.  The buffers are static: a ring of stacks = one hipGraph of the forward per stack."""
+    host synchronisation.  The buffers are static: a ring of stacks = one hipGraph of the forward per stack.
+
+    cameras = C > 1: the input of a RIG submission (`forward_async(..., cameras=C)`): B images, C consecutive ones per cloud, and cloud
+    tensors sized for B // C clouds.  `put_cloud(s, pyramid, feats)` fills cloud s and `put_image(f, img)` image f (it looks at cloud
+    f // C), one batched copy launch each; `put` writes a (cloud, image) pair and stays the call for cameras == 1."""
     KEYS = ("points", "neighbors", "subsampling", "upsampling")
 
-    def __init__(self, pyramid: Dict, feats: torch.Tensor, img: torch.Tensor, B: int):
+    def __init__(self, pyramid: Dict, feats: torch.Tensor, img: torch.Tensor, B: int, cameras: int = 1):
+        if cameras < 1 or B % cameras:
+            raise ValueError("a stack of B = %d images is no whole number of rigs of %d cameras" % (B, cameras))
         dev = feats.device
-        self.B = B
-        self.pyr = {k: [torch.empty((B * t.shape[0],) + tuple(t.shape[1:]), dtype=torch.float32 if k == "points" else torch.int32, device=dev)
+        self.B, self.cameras = B, cameras
+        S = self.clouds = B // cameras
+        self.pyr = {k: [torch.empty((S * t.shape[0],) + tuple(t.shape[1:]), dtype=torch.float32 if k == "points" else torch.int32, device=dev)
                         for t in pyramid[k]] for k in self.KEYS}
-        self.pyr["feats"] = torch.empty((B * feats.shape[0], feats.shape[1]), dtype=torch.float32, device=dev)
+        self.pyr["feats"] = torch.empty((S * feats.shape[0], feats.shape[1]), dtype=torch.float32, device=dev)
         self.img = torch.empty((B,) + tuple(img.shape[-3:]), dtype=torch.float32, device=dev)
         self._mc = ops.MultiCopy(dev)
         self._mc.MAX_TABLES = 1 << 16   # one cached descriptor table per (producer slot, frame position): a few hundred bytes each
 
+    def put_cloud(self, s: int, pyramid: Dict, feats: torch.Tensor):
+        """cloud s (0 <= s < B // cameras) <- the producer's tensors (int32 tables, contiguous), enqueued on the current stream"""
+        if not 0 <= s < self.clouds:
+            raise ValueError("cloud position %d outside the stack of %d" % (s, self.clouds))
+        srcs, dsts = [], []
+        for k in self.KEYS:
+            for t, d in zip(pyramid[k], self.pyr[k]):
+                n = t.shape[0]
+                srcs.append(t)
+                dsts.append(d[s * n:(s + 1) * n])
+        n = feats.shape[0]
+        self._mc.run(srcs + [feats], dsts + [self.pyr["feats"][s * n:(s + 1) * n]])
+
+    def put_image(self, f: int, img: torch.Tensor):
+        """image f (0 <= f < B; of cloud f // cameras) <- (3, H, W) or (1, 3, H, W); or images f .. f + n - 1 <- (n, 3, H, W), e.g. the C
+        images of a rig at once.  One batched copy launch, enqueued on the current stream."""
+        n = img.shape[0] if img.dim() == 4 else 1
+        if not 0 <= f <= self.B - n:
+            raise ValueError("frame positions %d .. %d outside the stack of %d" % (f, f + n - 1, self.B))
+        self._mc.run([img.reshape((n,) + tuple(self.img.shape[1:]))], [self.img[f:f + n]])
+
     def put(self, f: int, pyramid: Dict, feats: torch.Tensor, img: torch.Tensor):
         """frame f (0 <= f < B) <- the producer's tensors (int32 tables, contiguous), enqueued on the current stream"""
+        if self.cameras != 1:
+            raise ValueError("FrameStack(cameras=%d): put() fills a (cloud, image) pair; use put_cloud and put_image" % self.cameras)
         if not 0 <= f < self.B:
             raise ValueError("frame position %d outside the stack of %d" % (f, self.B))
         srcs, dsts = [], []

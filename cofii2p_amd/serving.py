@@ -25,6 +25,11 @@ frame's n matches): the poses of a whole stack are solved in one batched pass be
 Frames in, evaluation rows out (`evaluation.evaluate`): `FrameBatcher(model, pose=True, eval_table=table)`, `submit(pyr, img, K, P_gt=...,
 row=i)` with the frame's (4,4) ground-truth pose: the monitors of a stack (`evaluation.eval_monitors`, one launch) run behind its poses and
 frame i lands in row i of the `evaluation.EvalTable`; padding frames write nothing.  `drain()` waits for everything submitted.
+
+Rigs (one cloud under C images: the cameras around one sweep, a stereo pair): `FrameBatcher(model, batch=B, cameras=C)` with B a multiple
+of C, and `submit_rig(pyr, imgs (C,3,H,W), K (C,3,3), P_gt (C,4,4), rows)` -> C tickets, one per image, used like the tickets of `submit`.
+A stack then holds B // C clouds and B images and is submitted with `forward_async(..., cameras=C)`: the point encoder runs once per
+cloud.  A partly filled stack is completed with copies of its last RIG.
 """
 from typing import Dict, List, Optional, Tuple
 
@@ -36,10 +41,12 @@ from .preprocess import FrameStack
 
 class FrameBatcher:
     def __init__(self, model: CoFiI2P, batch: int = 16, streams: int = 4, ring: Optional[int] = None, slot_base: int = 200,
-                 pose: bool = False, pose_iterations: int = 10000, eval_table=None):
+                 pose: bool = False, pose_iterations: int = 10000, eval_table=None, cameras: int = 1):
         if batch < 1:
             raise ValueError("batch must be >= 1")
-        self.model, self.B = model, int(batch)
+        if cameras < 1 or batch % cameras:
+            raise ValueError("batch = %d is no whole number of rigs of cameras = %d" % (batch, cameras))
+        self.model, self.B, self.C = model, int(batch), int(cameras)
         self.S = max(1, int(streams))
         self.ring = int(ring) if ring is not None else 2 * self.S     # stacks: one being filled + the ones in flight
         if self.ring < 2:
@@ -88,16 +95,17 @@ class FrameBatcher:
 
     def _launch(self, j: int):
         st = self._stacks[j]
+        rig = {} if self.C == 1 else {"cameras": self.C}
         with torch.cuda.stream(self._stream(j)):
             if self.eval_table is not None:
                 self._handles[j] = self.model.forward_async(self.slot_base + j, st.pyr, st.img, inputs_stable=True, pose_K=self._K[j],
                                                             pose_iterations=self.pose_iterations,
-                                                            eval_into=(self.eval_table, self._P[j], self._row[j]))
+                                                            eval_into=(self.eval_table, self._P[j], self._row[j]), **rig)
             elif self.pose:
                 self._handles[j] = self.model.forward_async(self.slot_base + j, st.pyr, st.img, inputs_stable=True, pose_K=self._K[j],
-                                                            pose_iterations=self.pose_iterations)
+                                                            pose_iterations=self.pose_iterations, **rig)
             else:
-                self._handles[j] = self.model.forward_async(self.slot_base + j, st.pyr, st.img, inputs_stable=True)
+                self._handles[j] = self.model.forward_async(self.slot_base + j, st.pyr, st.img, inputs_stable=True, **rig)
         self._results[j] = self._poses[j] = self._fine[j] = self._counts[j] = None
         self._nsub += 1
 
@@ -133,6 +141,8 @@ class FrameBatcher:
         control to the caller's NEXT enqueue on that stream only - keep them unmodified until `result()` of any later ticket, or pass
         tensors that are not rewritten (a loader ring).  K: the frame's (3,3) camera matrix (host or device), required with pose=True.
         P_gt, row: the frame's (4,4) ground-truth pose (host or device) and its row of the evaluation table, required with eval_table."""
+        if self.C != 1:
+            raise ValueError("FrameBatcher(cameras=%d): submit() takes a (cloud, image) pair; a rig goes through submit_rig()" % self.C)
         if self.pose and K is None:
             raise ValueError("FrameBatcher(pose=True): submit() needs the frame's camera matrix K")
         if self.eval_table is not None and (P_gt is None or row is None or int(row) < 0):
@@ -167,17 +177,66 @@ class FrameBatcher:
             self._cur, self._fill = (j + 1) % self.ring, 0
         return ticket
 
+    def submit_rig(self, pc_data_dict: Dict, imgs: torch.Tensor, K=None, P_gt=None, rows=None) -> List[Tuple[int, int, int]]:
+        """one cloud and the C = cameras images that look at it -> C tickets, one per image (for `result`, `fine_xy`, `pose_result`).
+        imgs (C,3,H,W); K (C,3,3) camera matrices with pose=True; P_gt (C,4,4) ground-truth poses and rows (C table rows >= 0) with
+        eval_table.  The tensors are read as those of `submit` are."""
+        C = self.C
+        if not torch.is_tensor(imgs) or imgs.dim() != 4 or imgs.shape[0] != C:
+            raise ValueError("FrameBatcher(cameras=%d): submit_rig() needs the rig's images as one (%d,3,H,W) tensor, got %s"
+                             % (C, C, tuple(imgs.shape) if torch.is_tensor(imgs) else type(imgs).__name__))
+        if self.pose and (K is None or len(K) != C):
+            raise ValueError("FrameBatcher(pose=True): submit_rig() needs the images' camera matrices K (%d,3,3)" % C)
+        if self.eval_table is not None and (P_gt is None or rows is None or len(P_gt) != C or len(rows) != C or min(int(r) for r in rows) < 0):
+            raise ValueError("FrameBatcher(eval_table=...): submit_rig() needs the images' ground-truth poses P_gt (%d,4,4) and %d table rows >= 0" % (C, C))
+        j = self._cur
+        if self._fill == 0:
+            self._collect(j)
+            self._serial[j] += 1
+        cur = torch.cuda.current_stream(imgs.device)
+        s = self._stream(j)
+        s.wait_stream(cur)
+        with torch.cuda.stream(s):   # conversions on the submission's stream: see submit()
+            pyr = {k: ([CoFiI2P._as_idx32(t) for t in pc_data_dict[k]] if k != "points" else [p.contiguous() for p in pc_data_dict[k]])
+                   for k in FrameStack.KEYS}
+            feats = pc_data_dict["feats"].contiguous()
+            imgs = imgs.contiguous()
+            if self._stacks[j] is None:
+                self._stacks[j] = FrameStack(pyr, feats, imgs[0], self.B, cameras=C)
+            self._stacks[j].put_cloud(self._fill // C, pyr, feats)
+            self._stacks[j].put_image(self._fill, imgs)
+            for c in range(C):
+                f = self._fill + c
+                if self.pose:
+                    self._put_K(j, f, K[c])
+                if self.eval_table is not None:
+                    self._put_eval(j, f, P_gt[c], rows[c])
+        self._last = (pyr, feats, imgs)
+        tickets = [(j, self._serial[j], self._fill + c) for c in range(C)]
+        self._fill += C
+        if self._fill == self.B:
+            self._launch(j)
+            self._cur, self._fill = (j + 1) % self.ring, 0
+        return tickets
+
     def flush(self):
-        """submit the partly filled stack (padded with copies of its last frame)"""
+        """submit the partly filled stack (padded with copies of its last frame - of its last rig with cameras > 1)"""
         if self._fill == 0:
             return
         j = self._cur
         pyr, feats, img = self._last
         with torch.cuda.stream(self._stream(j)):
-            for f in range(self._fill, self.B):
-                self._stacks[j].put(f, pyr, feats, img)
-                if self.pose:
-                    self._K[j][f].copy_(self._K[j][self._fill - 1])
+            if self.C != 1:   # img: the last rig's (C,3,H,W); its camera matrices sit in the C rows before the first free one
+                for f0 in range(self._fill, self.B, self.C):
+                    self._stacks[j].put_cloud(f0 // self.C, pyr, feats)
+                    self._stacks[j].put_image(f0, img)
+                    if self.pose:
+                        self._K[j][f0:f0 + self.C].copy_(self._K[j][self._fill - self.C:self._fill])
+            else:
+                for f in range(self._fill, self.B):
+                    self._stacks[j].put(f, pyr, feats, img)
+                    if self.pose:
+                        self._K[j][f].copy_(self._K[j][self._fill - 1])
         self._launch(j)
         self._cur, self._fill = (j + 1) % self.ring, 0
 

@@ -531,6 +531,14 @@ int cofi_match_finish(const float *pts4, const float *pts1, int N1, const int32_
                       float *fine_xy, int32_t *best, int N4 /* rows of pts4 per frame */,
                       int frames /* stack mode: every array holds `frames` equally sized blocks (coarse_xy (frames, 2, ldxy), count_dev (frames, 2)) */,
                       cofi_stream_t stream);
+/* The same launch for a rig submission: frames = clouds x cameras images, image f looks at cloud f / cameras (the cameras of one cloud
+ * are consecutive; frames % cameras == 0, else COFI_EINVAL).  pts4, pts1 and fine_pc_all - the three operands that belong to the cloud -
+ * hold frames / cameras blocks; every other operand and every output is per image and laid out as cofi_match_finish lays it out.  Same
+ * kernel: cofi_match_finish is this entry with cameras = 1. */
+int cofi_match_finish_rig(const float *pts4, const float *pts1, int N1, const int32_t *sel, const int32_t *count_dev, int cap,
+                          const float *fmap, int ldf, int C, int H2, int W2, const float *coarse_xy, int ldxy, float center_scale,
+                          const float *fine_pc_all, int ldfpc, float *coarse_pts, float *patches, float *fine_pc, int ldo,
+                          float *fine_xy, int32_t *best, int N4, int frames, int cameras, cofi_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Row f3, first part: the training losses of model/loss.py with their gradients w.r.t. the network outputs
@@ -748,6 +756,16 @@ int cofi_resize_crop_image(const uint8_t *src_hwc, int src_h, int src_w, int dst
 /* Batched device-to-device copy in one launch: descs_dev = n records {const void *src; void *dst; uint64 bytes} in device
  * memory (e.g. the per-frame inputs -> the static buffers of a captured forward graph); blocks_per_copy workgroups per record. */
 int cofi_multi_copy(const void *descs_dev, int n, int blocks_per_copy, cofi_stream_t stream);
+
+/* Row blocks repeated in place of a caller-side torch.repeat_interleave: src holds `frames` blocks of rows_per_frame rows (leading
+ * dimension lds), dst `frames * times` such blocks (ldd), and
+ *   dst[(s * times + c) * rows_per_frame + r, 0:cols] = src[s * rows_per_frame + r, 0:cols]   for s < frames, c < times.
+ * Columns >= cols of dst are not touched: dst may be a column slice of a wider buffer (the coarse point tokens of one cloud copied
+ * into the transformer's (rows, 2 * 128) point stream once per camera of a rig).  16-byte accesses when both pointers and both leading
+ * dimensions are 16-byte aligned, with single floats for the cols % 4 rest; single floats throughout otherwise.  src and dst must not
+ * overlap. */
+int cofi_repeat_frames(const float *src, int lds, int rows_per_frame, int cols, int frames, int times, float *dst, int ldd,
+                       cofi_stream_t stream);
 
 #ifdef __cplusplus
 }
