@@ -10,13 +10,16 @@ namespace {
 
 // ---------------------------------------------------------------------------- GroupNorm stats
 // Level 1: block b reduces rows [b*ROWS, (b+1)*ROWS) for every group -> part[b][g] = {sum, sumsq}
-// (fp32 within a thread's <= ROWS*cpg values, fp64 across threads).  Level 2: one block combines
-// the partials in fp64 in a fixed order -> {mean, rstd}.  No atomics: bit-reproducible.
+// (the sum of a thread's own values in fp32, the squares and everything across threads in fp64).
+// Level 2: one block combines the partials in fp64 in a fixed order -> {mean, rstd}.  No atomics: bit-reproducible.
 constexpr int GS_ROWS = 64;
 
-// ACC = float: the serving path (a thread's <= 16 * cpg values in fp32, everything above in fp64).  ACC = double (cofi_group_stats_exact, the
+// A thread's own values: ROWS / 4 = 16 rows of one column (cpg < 64) or of cpg / 64 columns (cpg >= 64: 64 values at cpg = 256).
+// ACC = float: the serving path (the SUM of those values in fp32, everything above in fp64).  ACC = double (cofi_group_stats_exact, the
 // training path): the sums are exact to fp64, so the variance does not lose the digits E[x^2] - mean^2 cancels when |mean| >> std - the
 // backward of a normalisation removes a large component along the normalised input and amplifies a relative error of rstd by its size.
+// The squares are formed and summed in fp64 on both paths: an fp32 square is off by up to 2^-25 x^2, which E[x^2] - mean^2 does not cancel
+// - a group of ONE value (variance 0) came out with var = fl(x^2) - x^2 ~ 1e-7 against eps = 1e-5, rstd 1 % off.
 template <typename ACC>
 __global__ __launch_bounds__(256) void group_stats_partial_kernel(const float *x, int ldx, int M, int C, int groups, double *part) {
     // grid: x = row slab of GS_ROWS rows, y = 64-column tile (cpg < 64) or group (cpg >= 64), z = frame (M = rows per frame)
@@ -29,11 +32,12 @@ __global__ __launch_bounds__(256) void group_stats_partial_kernel(const float *x
     if (cpg < 64) {
         // lanes own columns of this tile; a group is cpg adjacent lanes (cpg is a power of two)
         const int c = blockIdx.y * 64 + lane;
-        ACC s = 0, q = 0;
+        ACC s = 0;
+        double q = 0;
         if (c < C)
             for (int r = r0 + wv; r < r1; r += 4) {
-                const ACC v = x[(size_t)r * ldx + c];
-                s += v;
+                const double v = x[(size_t)r * ldx + c];
+                s += (ACC)v;
                 q += v * v;
             }
         double ds = s, dq = q;
@@ -51,14 +55,15 @@ __global__ __launch_bounds__(256) void group_stats_partial_kernel(const float *x
         }
     } else {
         const int g = blockIdx.y;
-        ACC s = 0, q = 0;
+        ACC s = 0;
+        double q = 0;
         for (int r = r0 + wv; r < r1; r += 4)
             for (int c = g * cpg + lane; c < (g + 1) * cpg; c += 64) {
-                const ACC v = x[(size_t)r * ldx + c];
-                s += v;
+                const double v = x[(size_t)r * ldx + c];
+                s += (ACC)v;
                 q += v * v;
             }
-        const double ds = wave_sum_d((double)s), dq = wave_sum_d((double)q);
+        const double ds = wave_sum_d((double)s), dq = wave_sum_d(q);
         if (lane == 0) {
             red[wv][0][0] = ds;
             red[wv][0][1] = dq;
@@ -595,6 +600,12 @@ __global__ void pos_sine_kernel(PosArgs a) {
     }
 }
 
+// true if every non-null pointer is 16-byte aligned (operands the kernels read or write as float4)
+template <typename... P>
+inline bool aligned16(const P *...p) {
+    return (((uintptr_t)p | ...) & 15) == 0;
+}
+
 }  // namespace
 
 extern "C" int cofi_group_stats_from_colpart(const float *colpart, int nslab, int M, int C, int groups, float eps, float *stats,
@@ -657,6 +668,7 @@ static int group_norm_apply_entry(const float *x, int ldx, int M, int C, int gro
     if (!x || !stats || !y || M <= 0 || C <= 0 || groups <= 0 || (C % groups) || (C & 3) || (ldx & 3) || (ldy & 3)) return COFI_EINVAL;
     if ((gamma == nullptr) != (beta == nullptr) || (res_gamma == nullptr) != (res_beta == nullptr)) return COFI_EINVAL;
     if (res && (ldr & 3)) return COFI_EINVAL;
+    if (ldx < C || ldy < C || (res && ldr < C) || !aligned16(x, y, res)) return COFI_EINVAL;   // rows are read and written as float4
     if (frames <= 0 || (M % frames)) return COFI_EINVAL;
     const int Mf = M / frames;
     GnApplyArgs a{x, stats, gamma, beta, res, res_stats, res_gamma, res_beta, y, ldx, ldr, ldy, Mf, C, C / groups, slope, groups, row_pos, points, records};
@@ -704,6 +716,7 @@ static int group_norm_apply_partials_entry(const float *x, int ldx, int M, int C
                                            float4 *records, int frames, cofi_stream_t stream) {
     if (!x || !norm || !y || M <= 0 || C <= 0 || (C & 3) || (ldx & 3) || (ldy & 3) || ldx < C || ldy < C) return COFI_EINVAL;
     if (res && ((ldr & 3) || ldr < C)) return COFI_EINVAL;
+    if (!aligned16(x, y, res)) return COFI_EINVAL;   // rows are read and written as float4
     if (frames <= 0 || (M % frames) || (res_norm && !res)) return COFI_EINVAL;
     if (norm->channels != C || (res_norm && res_norm->channels != C) || (res_norm && res_norm->groups != norm->groups)) return COFI_EINVAL;
     const int Mf = M / frames, c4n = C >> 2, tpr = c4n < 256 ? c4n : 256, rpb = 256 / tpr;
@@ -743,6 +756,7 @@ extern "C" int cofi_layer_norm(const float *x, int ldx, int M, int C, const floa
                                const float *res, int ldr, float *y, int ldy, cofi_stream_t stream) {
     if (!x || !y || !gamma || !beta || M <= 0 || C <= 0 || C > 2048 || (C & 3) || (ldx & 3) || (ldy & 3) || (res && (ldr & 3)))
         return COFI_EINVAL;
+    if (ldx < C || ldy < C || (res && ldr < C) || !aligned16(x, y, res, gamma, beta)) return COFI_EINVAL;   // all five are read / written as float4
     hipLaunchKernelGGL(layer_norm_kernel, dim3(cofi_cdiv(M, 4)), dim3(256), 0, cofi_s(stream), x, ldx, M, C, gamma, beta, eps, relu ? 0.0f : 1.0f,
                        res, ldr, 0, y, ldy);
     return cofi_launch_status();
@@ -752,6 +766,7 @@ extern "C" int cofi_layer_norm_act(const float *x, int ldx, int M, int C, const 
                                    int ldr, int res_first, float *y, int ldy, cofi_stream_t stream) {
     if (!x || !y || !gamma || !beta || M <= 0 || C <= 0 || C > 2048 || (C & 3) || (ldx & 3) || (ldy & 3) || (res && (ldr & 3)) || !(slope >= 0.f && slope <= 1.f))
         return COFI_EINVAL;
+    if (ldx < C || ldy < C || (res && ldr < C) || !aligned16(x, y, res, gamma, beta)) return COFI_EINVAL;   // all five are read / written as float4
     hipLaunchKernelGGL(layer_norm_kernel, dim3(cofi_cdiv(M, 4)), dim3(256), 0, cofi_s(stream), x, ldx, M, C, gamma, beta, eps, slope, res, ldr,
                        res_first ? 1 : 0, y, ldy);
     return cofi_launch_status();

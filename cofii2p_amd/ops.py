@@ -192,9 +192,15 @@ def _p(t: Optional[torch.Tensor]):
     return None if t is None else ctypes.c_void_p(t.data_ptr())
 
 
-def _mat(t: torch.Tensor, name: str, dtype=torch.float32):
-    if not t.is_cuda:
-        raise _lib.CofiError("%s must be a CUDA (HIP) tensor — there is no CPU path" % name)
+def _on(t: torch.Tensor, device) -> bool:
+    """device: the device of the call's primary operand (already checked), which `t` has to share; None: any CUDA device."""
+    return t.is_cuda if device is None else t.device == device
+
+
+def _mat(t: torch.Tensor, name: str, dtype=torch.float32, device=None):
+    if not _on(t, device):
+        raise _lib.CofiError("%s must be a CUDA (HIP) tensor — there is no CPU path" % name if device is None
+                             else "%s is on %s, the call runs on %s" % (name, t.device, device))
     if t.dtype != dtype or t.dim() != 2 or (t.shape[1] > 1 and t.stride(1) != 1):
         raise _lib.CofiError("%s: expected row-major 2-D %s, got %s %s stride %s" % (name, dtype, t.dtype, tuple(t.shape), t.stride()))
     return t
@@ -204,12 +210,42 @@ def _ld(t: torch.Tensor) -> int:
     return t.stride(0) if t.shape[0] > 1 else max(t.stride(0), t.shape[1])
 
 
-def _vec(t: Optional[torch.Tensor], name: str, n: int, dtype=torch.float32):
+def _vec(t: Optional[torch.Tensor], name: str, n: int, dtype=torch.float32, device=None):
     if t is None:
         return None
-    if not t.is_cuda or t.dtype != dtype or t.numel() != n or not t.is_contiguous():
-        raise _lib.CofiError("%s: expected contiguous CUDA %s of %d elements" % (name, dtype, n))
+    if not _on(t, device) or t.dtype != dtype or t.numel() != n or not t.is_contiguous():
+        raise _lib.CofiError("%s: expected contiguous %s %s of %d elements" % (name, "CUDA" if device is None else device, dtype, n))
     return t
+
+
+def _norm_operands(what: str, x: torch.Tensor, frames: int = 1, gamma=None, beta=None, res=None, res_gamma=None, res_beta=None, stats=None,
+                   res_stats=None, out=None):
+    """Everything a normalisation kernel reads or writes besides `x` (already through _mat), judged by tensor metadata alone: the kernels
+    index gamma / beta by channel, res / out by the rows and columns of x and the statistics by (frame, group) without any bound of their
+    own, so a short or misplaced operand would be an out-of-bounds access.  ColStats statistics are checked by their own descriptor."""
+    M, C = x.shape
+    dev = x.device
+    for name, v in (("gamma", gamma), ("beta", beta), ("res_gamma", res_gamma), ("res_beta", res_beta)):
+        _vec(v, "%s: %s" % (what, name), C, device=dev)
+    for name, t in (("res", res), ("out", out)):
+        if t is not None:
+            _mat(t, "%s: %s" % (what, name), device=dev)
+            if tuple(t.shape) != (M, C):
+                raise _lib.CofiError("%s: %s is %s, x is %s" % (what, name, tuple(t.shape), (M, C)))
+    groups = None
+    for name, s in (("stats", stats), ("res_stats", res_stats)):
+        if s is None or isinstance(s, ColStats):
+            if name == "stats" and s is not None:
+                groups = s.groups
+            continue
+        if s.device != dev or s.dtype != torch.float32 or not s.is_contiguous() or s.dim() not in (2, 3) or s.shape[-1] != 2:
+            raise _lib.CofiError("%s: %s must be a contiguous fp32 (groups, 2) or (frames, groups, 2) tensor on %s" % (what, name, dev))
+        g = s.shape[-2]
+        if g == 0 or C % g or s.numel() != frames * g * 2 or (groups is not None and g != groups):
+            raise _lib.CofiError("%s: %s %s does not hold %d frame(s) of groups that divide %d channels%s"
+                                 % (what, name, tuple(s.shape), frames, C, "" if groups is None else " (%d groups, as stats)" % groups))
+        if name == "stats":
+            groups = g
 
 
 class Workspace:
@@ -709,6 +745,7 @@ def group_norm_apply(x, stats, gamma=None, beta=None, slope: float = 1.0, res=No
     lib = _lib.load()
     _mat(x, "x")
     M, C = x.shape
+    _norm_operands("group_norm_apply", x, frames, gamma, beta, res, res_gamma, res_beta, stats, res_stats, out)
     if out is None:
         out = torch.empty((M, C), dtype=torch.float32, device=x.device)
     for stale in ("cofi_row_pos", "cofi_kp_records"):   # a reused `out` must not carry what an earlier call attached
@@ -763,6 +800,7 @@ def layer_norm(x, gamma, beta, relu: bool = False, res=None, out=None, eps: floa
     lib = _lib.load()
     _mat(x, "x")
     M, C = x.shape
+    _norm_operands("layer_norm", x, gamma=gamma, beta=beta, res=res, out=out)
     if out is None:
         out = torch.empty((M, C), dtype=torch.float32, device=x.device)
     if M == 0:
@@ -778,6 +816,7 @@ def layer_norm_act(x, gamma, beta, slope: float = 1.0, res=None, res_first: bool
     lib = _lib.load()
     _mat(x, "x")
     M, C = x.shape
+    _norm_operands("layer_norm_act", x, gamma=gamma, beta=beta, res=res, out=out)
     if out is None:
         out = torch.empty((M, C), dtype=torch.float32, device=x.device)
     if M == 0:
@@ -828,6 +867,19 @@ def col_mean(x, frames: int = 1):
     return out
 
 
+def _transpose_out(out: torch.Tensor, device, frames: int, C: int, M: int):
+    """A caller's destination of transpose(), by metadata alone: (C, M) rows of unit stride, or (frames, C, M) whose frame blocks follow
+    one another at C rows' distance (the kernel steps C * ldy from frame to frame)."""
+    if out.dim() == 2 and frames == 1:
+        _mat(out, "transpose: out", device=device)
+    elif (out.dim() != 3 or out.device != device or out.dtype != torch.float32 or (M > 1 and out.stride(2) != 1)
+          or (frames > 1 and out.stride(0) != C * out.stride(1))):
+        raise _lib.CofiError("transpose: out must be fp32 (frames, C, M) on %s with unit inner stride and frames C rows apart, got %s stride %s"
+                             % (device, tuple(out.shape), out.stride()))
+    if tuple(out.shape) != ((C, M) if out.dim() == 2 else (frames, C, M)) or (C > 1 and out.stride(-2) < M):
+        raise _lib.CofiError("transpose: out is %s stride %s, expected %s" % (tuple(out.shape), out.stride(), (frames, C, M)))
+
+
 def transpose(x, out=None, frames: int = 1):
     """(M, C) -> (C, M); frames > 1: x holds `frames` row blocks of M / frames rows, out = (frames, C, M / frames), one launch."""
     lib = _lib.load()
@@ -838,6 +890,8 @@ def transpose(x, out=None, frames: int = 1):
     M //= frames
     if out is None:
         out = torch.empty((C, M) if frames == 1 else (frames, C, M), dtype=torch.float32, device=x.device)
+    else:
+        _transpose_out(out, x.device, frames, C, M)
     _lib.check(lib.cofi_transpose(_p(x), _ld(x), M, C, _p(out), out.stride(-2), frames, _stream()), "cofi_transpose")
     return out
 

@@ -293,6 +293,8 @@ int cofi_gemm_f32_layernorm(const float *A, int lda, const float *W, int ldw, fl
  *   R = res                            if res != NULL and res_stats == NULL
  *   R = gn(res; res_stats, rg, rb)     otherwise        (modules.py:222-240 residual tail)
  * slope = 1 is the identity, 0 is ReLU, 0.1 the reference's LeakyReLU.
+ * The apply entry points read and write rows as float4: C, ldx, ldr, ldy multiples of 4 and >= C, x / res / y 16-byte aligned
+ * (COFI_EINVAL otherwise).
  */
 int cofi_group_stats_from_colpart(const float *colpart, int nslab, int M, int C, int groups, float eps, float *stats, int frames,
                                   cofi_stream_t stream);
@@ -330,7 +332,8 @@ int cofi_group_norm_apply_partials_rec(const float *x, int ldx, int M, int C, co
                                        cofi_stream_t stream);
 
 /* Row LayerNorm: y = act(LN(x) * gamma + beta) (+ res).  Replaces nn.LayerNorm at
- * model/transformer/transformer.py:40-41,58,62 and model/network.py:29.  C <= 2048, C % 4 == 0. */
+ * model/transformer/transformer.py:40-41,58,62 and model/network.py:29.  C <= 2048, C % 4 == 0; ldx / ldr / ldy multiples of 4
+ * and >= C; x, res, y, gamma and beta 16-byte aligned (all are accessed as float4). */
 /* cofi_layer_norm_act: the general form, y = leaky(LN(x) * gamma + beta + R1, slope) + R2 with R1 = res if res_first else 0 and
  * R2 = res otherwise; slope 1 = no activation, 0 = ReLU, 0.1 = the point encoder's LeakyReLU (the 'ln' configuration of
  * model/kpconv/modules.py:51-60: UnaryBlock / ConvBlock / the residual join of ResidualBlock). */
