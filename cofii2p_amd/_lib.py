@@ -160,6 +160,7 @@ SIGNATURES = {
     "cofi_radius_mask": (_I, [_P, _P, _I, _I, _I, _F, ctypes.c_longlong, ctypes.c_longlong, _P, _P, _P]),
     "cofi_gather_transform": (_I, [_P, _P, _I, _P, _P, _P, _I, _P]),
     "cofi_resize_crop_image": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
+    "cofi_estimate_normals": (_I, [_P, _I, _P, _P, _I, _I, _I, _F, _P, _P, ctypes.c_longlong, ctypes.c_longlong, _P, _P]),
 }
 
 

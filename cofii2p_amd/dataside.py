@@ -28,6 +28,7 @@ import numpy as np
 import torch
 
 from . import _lib, ops
+from .normals import estimate_normals
 from .preprocess import build_pyramid
 
 VOXEL_SIZE = 0.1   # kitti.py:283
@@ -131,23 +132,51 @@ class FramePreparer:
     the tensors on the device (`img` (3,H,W), `pc_data_dict` with int64 tables and `feats`, the label tensors, K / K_4 / P).
     Buffers are cached per input size; one preparer per stream."""
 
-    def __init__(self, opt, device="cuda", mode: str = "val", dataset: str = "kitti"):
+    def __init__(self, opt, device="cuda", mode: str = "val", dataset: str = "kitti", normals: str = "given", normals_k: int = 30,
+                 normals_radius: Optional[float] = None):
         """dataset: 'kitti' (data/kitti.py: calibration transform, voxel grid, normals as features) or 'nuscenes' (data/nuscenes.py:177-320:
-        the stored cloud is already in the camera frame and is resampled directly, features = [intensity | point], seed = index)."""
+        the stored cloud is already in the camera frame and is resampled directly, features = [intensity | point], seed = index).
+        normals (KITTI only): 'given' - the scan is (7, N) and carries its normals, as the reference's pc_npy_with_normal file does;
+        'estimate' - the scan is (4, N) = [xyz | intensity] (a velodyne .bin, a live scan) and the normals are estimated from the
+        normals_k nearest points (within normals_radius, if given) in the sensor frame, oriented towards the sensor at the origin
+        (cofii2p_amd/normals.py); rows 4..6 of a (7, N) scan are then ignored and recomputed."""
         if mode not in ("val", "train"):
             raise ValueError("mode must be 'val' or 'train'")
         if dataset not in ("kitti", "nuscenes"):
             raise ValueError("dataset name invalid, only support KITTI Odometry and Nuscenes now!")   # train.py:130
+        if normals not in ("given", "estimate"):
+            raise ValueError("normals must be 'given' or 'estimate'")
         self.dataset = dataset
+        self.normals, self.normals_k, self.normals_radius = normals, normals_k, normals_radius
         self.opt, self.device, self.mode = opt, torch.device(device), mode
         self._ws = ops.Workspace()
-        self._rows = self._vox = None
+        self._rows = self._vox = self._scan7 = self._scan_pts = None
         self.last = {}
+
+    def scan_with_normals(self, data: torch.Tensor) -> torch.Tensor:
+        """normals='estimate': (4, N) or (7, N) device scan -> the preparer's (7, N) scan [xyz | intensity | estimated normal], overwritten by the
+        next call (enqueued, no host wait; the input is not modified)"""
+        if data.dim() != 2 or data.shape[0] not in (4, 7) or data.dtype != torch.float32 or not data.is_contiguous() or not data.is_cuda:
+            raise _lib.CofiError("dataside: with normals='estimate' the raw scan must be a contiguous (4, N) or (7, N) float32 tensor")
+        N = data.shape[1]
+        if self._scan7 is None or self._scan7.shape[1] != N:   # cached per input size like the row buffers (one begin() in flight per preparer)
+            self._scan7 = torch.empty((7, N), dtype=torch.float32, device=data.device)
+            self._scan_pts = torch.empty((N, 3), dtype=torch.float32, device=data.device)
+        d7, pts = self._scan7, self._scan_pts
+        d7[:4] = data[:4]
+        pts.copy_(data[:3].t())
+        # sensor frame, before the calibration transform: the sensor sits at the origin there; the kernel writes rows 4..6 in place.  The
+        # k-nearest grid, its order and the (N, k) index table are allocated per call inside estimate_normals (the caching allocator's).
+        estimate_normals(pts, self.normals_k, self.normals_radius, out=d7[4:7].t())
+        return d7
 
     def voxel_downsample(self, data: torch.Tensor, P_Tr: torch.Tensor, wait: bool = True):
         """(7, N) raw scan + 4x4 calibration transform (device) -> ((cap, 8) voxel rows, count).  wait=True syncs on the count;
-        wait=False returns (rows, pinned host counters, event) - read the counters after event.synchronize()."""
+        wait=False returns (rows, pinned host counters, event) - read the counters after event.synchronize().  With normals='estimate' the
+        scan is (4, N) and its normals are estimated first."""
         lib = _lib.load()
+        if self.normals == "estimate":
+            data = self.scan_with_normals(data)
         if data.dim() != 2 or data.shape[0] != 7 or data.dtype != torch.float32 or not data.is_contiguous():
             raise _lib.CofiError("dataside: the raw scan must be a contiguous (7, N) float32 tensor")
         N = data.shape[1]

@@ -41,15 +41,18 @@ class _Slot:
 
 class FrameLoader:
     def __init__(self, opt, device="cuda", slots: int = 8, workers: int = 4, dataset: str = "kitti", capture_stream: Optional[torch.cuda.Stream] = None,
-                 upsample_k: Optional[int] = None, mode: str = "val"):
+                 upsample_k: Optional[int] = None, mode: str = "val", normals: str = "given", normals_k: int = 30,
+                 normals_radius: Optional[float] = None):
         """slots: frames that can be in preparation / flight at once (a slot is reusable once the forward that read its tensors has been
         collected).  capture_stream: the stream hipGraphs are captured on (pass the model's: `model.frame_streams(n)[0]`); capture
-        needs a non-default stream and every extra stream costs a hardware queue."""
+        needs a non-default stream and every extra stream costs a hardware queue.  normals / normals_k / normals_radius: handed to the
+        slots' preparers (dataside.FramePreparer: 'estimate' takes (4, N) KITTI scans and estimates the normals in begin())."""
         self.opt, self.device, self.dataset, self.mode = opt, torch.device(device), dataset, mode
         # upsample_k=1: the up-sampling tables hold their first column only (all the forward reads), derived without a search
         # (preprocess.build_pyramid); None: the reference's (N, 128) tables
         self.upsample_k = upsample_k
-        self.preps = [dataside.FramePreparer(opt, device, dataset=dataset, mode=mode) for _ in range(slots)]
+        self.preps = [dataside.FramePreparer(opt, device, dataset=dataset, mode=mode, normals=normals, normals_k=normals_k,
+                                                normals_radius=normals_radius) for _ in range(slots)]
         self.slots = [_Slot() for _ in range(slots)]
         workers = self.worker_budget(workers)
         self.workers = workers

@@ -755,6 +755,24 @@ int cofi_gather_transform(const float *vox_rows, const int32_t *choice, int n, c
                           cofi_stream_t stream);
 int cofi_resize_crop_image(const uint8_t *src_hwc, int src_h, int src_w, int dst_h, int dst_w, int crop_y, int crop_x, int H, int W,
                            float *out_chw, cofi_stream_t stream);
+/* Surface normals for a scan that comes without them (a velodyne .bin, a live scan): the reference reads the normal from its
+ * pc_npy_with_normal file (kitti.py:130) and computes it nowhere, so this contract is the project's own; parity with the third-party
+ * estimator of the upstream preprocessing is unpinned.
+ *   points (S, 3); idx (Q, ldi) int32 rows into points, dist (Q, ldi) their squared distances (NULL allowed when radius <= 0): row q is
+ *       the neighbourhood of point q (Q <= S), as a self search cofi_knn_topk_grid / cofi_knn_topk returns it; the first k slots of a row
+ *       are read (k <= 128, ldi >= k).  A slot is skipped when its index is >= S (the search's shadow padding) or, with radius > 0, its
+ *       squared distance is > radius^2 ("at most k within radius"); m = slots kept.
+ *   fp32: d = neighbour - query, C = sum d d^T / m - (sum d / m)(sum d / m)^T, normal = unit eigenvector of the smallest eigenvalue of C
+ *       (cyclic Jacobi on the power-of-two scaled matrix + one first-order correction against the unrotated matrix).
+ *   degenerate rows - m < 3, trace(C) == 0 (all neighbours coincide) or a non-finite result - get (0, 0, 1) and are counted into
+ *       degenerate_count_dev[0] (optional; zeroed by the caller; one atomic per wave at most).
+ *   sign: the component of largest magnitude positive (lowest axis on ties); then, with viewpoint3_dev (3 floats in device memory, NULL for
+ *       none), flipped when n . (v - p) < 0.  A function of the input alone.
+ *   out[q * out_point_stride + c * out_comp_stride], c = 0..2 (strides in floats): (N, 3) rows are (3, 1); rows 4..6 of a channel-major
+ *       (7, N) scan are written in place with out = data7n + 4 * N, strides (1, N). */
+int cofi_estimate_normals(const float *points, int S, const int32_t *idx, const float *dist, int Q, int k, int ldi, float radius,
+                          const float *viewpoint3_dev, float *out, long long out_point_stride, long long out_comp_stride,
+                          int32_t *degenerate_count_dev, cofi_stream_t stream);
 
 /* Batched device-to-device copy in one launch: descs_dev = n records {const void *src; void *dst; uint64 bytes} in device
  * memory (e.g. the per-frame inputs -> the static buffers of a captured forward graph); blocks_per_copy workgroups per record. */
