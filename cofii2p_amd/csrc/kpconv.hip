@@ -11,6 +11,17 @@
 //     bytes of one row, so the gather is served in coalesced 64-B segments from L2.
 // Nothing is staged through LDS and the (M,H,15) influence tensor / (M,H,C) gather of the reference
 // never exist in memory.  Channel passes of 16*NACC channels go over gridDim.y.
+//
+// The four aggregation kernels (kpconv_aggregate_kernel, _shared_kernel, _c4_kernel, kpconv_fused_kernel) promise identical bits; they keep
+// the promise by running the SAME bodies, each defined once:
+//   kp_query          query position, this lane's kernel point, 1 / sigma, the support radius     (all four)
+//   kp_shift_frame    stack mode: support bases of the query's frame                              (general, shared, fused)
+//   kp_support        one support row's position and flag, from a record or from separate arrays  (general, shared, fused)
+//   kp_compact / kp_shadow   survivors into LDS records in neighbour order, shadow records behind  (general, shared, fused; c4 fills two arrays)
+//   kp_steps          the pipelined feature-load / MFMA loop over the records                     (general, shared, fused)
+//   kp_store          = kp_store_rows (fp32 or bf16 planes, via kp_split_store) + kp_store_cnt    (general, shared; c4 the count; fused
+//                       kp_split_store into its LDS tile and kp_count)
+// (general, fused: through kp_aggregate_query).  Host side: kp_args names every KpArgs field once, kp_check_support is the addressing limit.
 #include "bf16_split.h"
 #include "common.h"
 #include <stdlib.h>
@@ -134,30 +145,82 @@ __device__ __forceinline__ void kp_steps(const char *fbase, const unsigned ldfb,
     }
 }
 
+// What a wave knows of its query m before it looks at a neighbour: the query's position, kernel point j of this lane, 1 / sigma and the
+// squared support radius.
+struct KpQuery {
+    float qx, qy, qz, kx, ky, kz, inv_sigma, rsup2;
+};
+
+__device__ __forceinline__ KpQuery kp_query(const KpArgs &a, const int m, const int j) {
+    KpQuery q;
+    q.qx = a.q_pts[3 * m]; q.qy = a.q_pts[3 * m + 1]; q.qz = a.q_pts[3 * m + 2];
+    // MFMA row 15 (lane j == 15) is a padding row that is never stored: it may hold any finite weight
+    const int jk = j < 15 ? j : 0;
+    q.kx = a.kp[3 * jk]; q.ky = a.kp[3 * jk + 1]; q.kz = a.kp[3 * jk + 2];
+    q.inv_sigma = 1.0f / a.sigma;
+    // Support of the kernel: the influence max(0, 1 - |d - k| / sigma) of EVERY kernel point k is exactly 0 for a neighbour at |d| >=
+    // max|k| + sigma.  The k nearest neighbours of the pyramid reach far beyond that (KITTI-shaped frames: 2 - 26 % of the 128 lie
+    // inside), so the staging keeps only the neighbours inside the support (compacted, order preserved) and the MFMA / feature-load
+    // loop runs over those: exact - the dropped terms are zeros - up to the regrouping of the fp32 sums.  (The bound carries a 2e-5
+    // margin: far more than the rounding of the distances on either side.)
+    float kn = j < 15 ? __builtin_amdgcn_sqrtf((q.kx * q.kx + q.ky * q.ky) + q.kz * q.kz) : 0.f;
+#pragma unroll
+    for (int o = 8; o > 0; o >>= 1) kn = fmaxf(kn, __shfl_xor(kn, o, 64));
+    const float rsup = (kn + a.sigma) * 1.00002f;
+    q.rsup2 = rsup * rsup;
+    return q;
+}
+
+// Stack mode: shift the support-side bases of a (a kernel's private copy) to the frame of query m (indices are frame-local).
+// REC: the support is a.recs, else a.s_pts / a.row_pos.
+template <bool REC>
+__device__ __forceinline__ void kp_shift_frame(KpArgs &a, const int m) {
+    const size_t fo = (size_t)(m / a.Mpf) * a.N;
+    a.feats += fo * a.ldf;
+    if constexpr (REC) {
+        a.recs += fo;
+    } else {
+        a.s_pts += fo * 3;
+        a.row_pos += fo;
+    }
+}
+
+// Position and positive-sum flag of support row idc: ONE 16-byte record (REC) or three position dwords and the flag byte.
+template <bool REC>
+__device__ __forceinline__ void kp_support(const KpArgs &a, const int idc, float &px, float &py, float &pz, int &pos) {
+    if constexpr (REC) {
+        const float4 rv = a.recs[idc];
+        px = rv.x; py = rv.y; pz = rv.z;
+        pos = rv.w != 0.f;
+    } else {
+        const float *sp = a.s_pts + 3 * (size_t)idc;
+        px = sp[0]; py = sp[1]; pz = sp[2];
+        pos = a.row_pos[idc];
+    }
+}
+
+// Compaction: the lanes with `inside` append their record r behind the nin records already in rec, in lane order.  -> the new nin.
+__device__ __forceinline__ int kp_compact(float4 *rec, const int nin, const bool inside, const float4 r) {
+    const unsigned long long msk = __ballot(inside);
+    if (inside) rec[nin + __popcll(msk & ((1ull << (threadIdx.x & 63)) - 1ull))] = r;
+    return nin + __popcll(msk);
+}
+
+// 64 shadow records (1e18 away: influence exactly 0, row 0: finite data) behind the nin records, so the step loop needs no validity test
+__device__ __forceinline__ void kp_shadow(float4 *rec, const int nin) {
+    rec[nin + (threadIdx.x & 63)] = make_float4(1e18f, 0.f, 0.f, __int_as_float(0));
+}
+
 // The aggregation of ONE query m by one wave (see the file header): acc[ch][v] = MFMA accumulators (rows = kernel points,
 // column j = channel c0 + ch*16*VEC + VEC*j + v), npos = neighbours whose feature row sums to > 0 (kpconv.py:113-114).
 // rec = the wave's private LDS record buffer (PHASE + KP_PAD entries); a is a private copy (frame shift).
-// REC: the staging reads ONE 16-byte record per neighbour (a.recs) instead of three position dwords and the flag byte - the
-// same differences, the same list, the same order: identical bits.
 template <int VEC, int NCH, int PHASE, bool REC>
 __device__ __forceinline__ void kp_aggregate_query(KpArgs a, const int m, const int c0, float4 *rec, f32x4 (&acc)[NCH][VEC], int &npos) {
     constexpr int KP_PHASE = PHASE;
     const int lane = threadIdx.x & 63;
     const int j = lane & 15;
-    {   // stack mode: shift the support-side bases to this query's frame (indices are frame-local)
-        const size_t fo = (size_t)(m / a.Mpf) * a.N;
-        a.feats += fo * a.ldf;
-        if constexpr (REC) {
-            a.recs += fo;
-        } else {
-            a.s_pts += fo * 3;
-            a.row_pos += fo;
-        }
-    }
-    const float qx = a.q_pts[3 * m], qy = a.q_pts[3 * m + 1], qz = a.q_pts[3 * m + 2];
-    // MFMA row 15 (lane j == 15) is a padding row that is never stored: it may hold any finite weight
-    const int jk = j < 15 ? j : 0;
-    const float kx = a.kp[3 * jk], ky = a.kp[3 * jk + 1], kz = a.kp[3 * jk + 2];
+    kp_shift_frame<REC>(a, m);
+    const KpQuery q = kp_query(a, m, j);
 #pragma unroll
     for (int ch = 0; ch < NCH; ++ch)
 #pragma unroll
@@ -175,20 +238,6 @@ __device__ __forceinline__ void kp_aggregate_query(KpArgs a, const int m, const 
     }
     const char *fbase = reinterpret_cast<const char *>(a.feats);
     const unsigned ldfb = 4u * a.ldf;
-    const float inv_sigma = 1.0f / a.sigma;
-    // Support of the kernel: the influence max(0, 1 - |d - k| / sigma) of EVERY kernel point k is exactly 0 for a neighbour at |d| >=
-    // max|k| + sigma.  The k nearest neighbours of the pyramid reach far beyond that (KITTI-shaped frames: 2 - 26 % of the 128 lie
-    // inside), so the staging keeps only the neighbours inside the support (compacted, order preserved) and the MFMA / feature-load
-    // loop runs over those: exact - the dropped terms are zeros - up to the regrouping of the fp32 sums.  (The bound carries a 2e-5
-    // margin: far more than the rounding of the distances on either side.)
-    float rsup;
-    {
-        float kn = j < 15 ? __builtin_amdgcn_sqrtf((kx * kx + ky * ky) + kz * kz) : 0.f;
-#pragma unroll
-        for (int o = 8; o > 0; o >>= 1) kn = fmaxf(kn, __shfl_xor(kn, o, 64));
-        rsup = (kn + a.sigma) * 1.00002f;
-    }
-    const float rsup2 = rsup * rsup;
 
     for (int h0 = 0; h0 < a.H; h0 += KP_PHASE) {
         const int nh = a.H - h0 < KP_PHASE ? a.H - h0 : KP_PHASE;  // multiple of 4
@@ -203,36 +252,94 @@ __device__ __forceinline__ void kp_aggregate_query(KpArgs a, const int m, const 
         float px[KP_PHASE / 64], py[KP_PHASE / 64], pz[KP_PHASE / 64];
         int pos[KP_PHASE / 64];
 #pragma unroll
-        for (int r = 0; r < KP_PHASE / 64; ++r) {
-            const int idc = (unsigned)idr[r] < (unsigned)a.N ? idr[r] : 0;
-            if constexpr (REC) {
-                const float4 rv = a.recs[idc];
-                px[r] = rv.x; py[r] = rv.y; pz[r] = rv.z;
-                pos[r] = rv.w != 0.f;
-            } else {
-                const float *sp = a.s_pts + 3 * (size_t)idc;
-                px[r] = sp[0]; py[r] = sp[1]; pz[r] = sp[2];
-                pos[r] = a.row_pos[idc];
-            }
-        }
+        for (int r = 0; r < KP_PHASE / 64; ++r) kp_support<REC>(a, (unsigned)idr[r] < (unsigned)a.N ? idr[r] : 0, px[r], py[r], pz[r], pos[r]);
         int nin = 0;   // neighbours of this phase inside the kernel's support (wave-uniform)
 #pragma unroll
         for (int r = 0; r < KP_PHASE / 64; ++r) {
             const bool valid = (unsigned)idr[r] < (unsigned)a.N;
             npos += __popcll(__ballot(valid && pos[r] != 0));   // kpconv.py:113-115 counts over ALL neighbours
             // kpconv.py:93: neighbours centred on the query
-            const float dx = px[r] - qx, dy = py[r] - qy, dz = pz[r] - qz;
-            const bool inside = valid && (dx * dx + dy * dy) + dz * dz < rsup2;
-            const unsigned long long msk = __ballot(inside);
-            if (inside) rec[nin + __popcll(msk & ((1ull << lane) - 1ull))] = make_float4(dx, dy, dz, __int_as_float(idr[r]));
-            nin += __popcll(msk);
+            const float dx = px[r] - q.qx, dy = py[r] - q.qy, dz = pz[r] - q.qz;
+            const bool inside = valid && (dx * dx + dy * dy) + dz * dz < q.rsup2;
+            nin = kp_compact(rec, nin, inside, make_float4(dx, dy, dz, __int_as_float(idr[r])));
         }
-        // shadow records (1e18 away: influence exactly 0, row 0: finite data) behind the list, so the step loop needs no validity test
-        rec[nin + lane] = make_float4(1e18f, 0.f, 0.f, __int_as_float(0));
+        kp_shadow(rec, nin);
         __builtin_amdgcn_wave_barrier();
-        kp_steps<VEC, NCH>(fbase, ldfb, coffb, rec, nin, kx, ky, kz, inv_sigma, acc);
+        kp_steps<VEC, NCH>(fbase, ldfb, coffb, rec, nin, q.kx, q.ky, q.kz, q.inv_sigma, acc);
         __builtin_amdgcn_wave_barrier();
     }
+}
+
+// The bf16 hi / lo planes (same rounding as the GEMM's on-the-fly split: identical products) of the VEC adjacent channels that a lane
+// holds of accumulator row r, to hi and lo: VEC bf16 each, packed in pairs.
+template <int VEC>
+__device__ __forceinline__ void kp_split_store(const f32x4 (&acc)[VEC], const int r, uint16_t *hi_dst, uint16_t *lo_dst) {
+    if constexpr (VEC == 4) {
+        uint2 hi, lo;
+        cofi_split2(acc[0][r], acc[1][r], hi.x, lo.x);
+        cofi_split2(acc[2][r], acc[3][r], hi.y, lo.y);
+        *reinterpret_cast<uint2 *>(hi_dst) = hi;
+        *reinterpret_cast<uint2 *>(lo_dst) = lo;
+    } else if constexpr (VEC == 2) {
+        unsigned hi, lo;
+        cofi_split2(acc[0][r], acc[1][r], hi, lo);
+        *reinterpret_cast<unsigned *>(hi_dst) = hi;
+        *reinterpret_cast<unsigned *>(lo_dst) = lo;
+    } else {
+        unsigned hi, lo;
+        cofi_split2(acc[0][r], 0.f, hi, lo);
+        hi_dst[0] = (uint16_t)hi;
+        lo_dst[0] = (uint16_t)lo;
+    }
+}
+
+// The store of one query's accumulators (channels from c0, see kp_aggregate_query) to row m of a.agg: fp32 (M, ld_agg), or with PLANES
+// the bf16 hi plane (M, ld_agg bf16) and the lo plane a.planes_lo elements behind it.  CHECK_C: a.C may end inside this pass.
+// The lane ids are taken HERE, after the step loop, so that nothing of the store addresses occupies registers across it.
+template <int VEC, int NCH, bool CHECK_C, bool PLANES>
+__device__ __forceinline__ void kp_store_rows(const KpArgs &a, const int m, const int c0, const f32x4 (&acc)[NCH][VEC]) {
+    const int lane = __lane_id() & 63, j = lane & 15, g = lane >> 4;   // & 63: g <= 3 is known, three of the four k < 15 tests fold away
+    // D layout 16x16: row (kernel point) = 4*g + r, col = j  ->  channels c .. c+VEC-1 contiguous
+    float *orow = a.agg + (size_t)m * a.ld_agg;
+    uint16_t *hrow = reinterpret_cast<uint16_t *>(a.agg) + (size_t)m * a.ld_agg;
+#pragma unroll
+    for (int ch = 0; ch < NCH; ++ch) {
+        const int c = c0 + ch * 16 * VEC + VEC * j;
+        if (!CHECK_C || c < a.C) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int k = 4 * g + r;
+                if (k < 15) {
+                    const size_t o = (size_t)k * a.C + c;
+                    if constexpr (PLANES)
+                        kp_split_store<VEC>(acc[ch], r, hrow + o, hrow + o + a.planes_lo);
+                    else if constexpr (VEC == 4)
+                        *reinterpret_cast<float4 *>(orow + o) = make_float4(acc[ch][0][r], acc[ch][1][r], acc[ch][2][r], acc[ch][3][r]);
+                    else if constexpr (VEC == 2)
+                        *reinterpret_cast<float2 *>(orow + o) = make_float2(acc[ch][0][r], acc[ch][1][r]);
+                    else
+                        orow[o] = acc[ch][0][r];
+                }
+            }
+        }
+    }
+}
+
+// kpconv.py:113-115: the divisor of a query with npos neighbours of positive feature sum, and its store for query m
+__device__ __forceinline__ float kp_count(const int npos) { return (float)(npos > 1 ? npos : 1); }
+
+__device__ __forceinline__ void kp_store_cnt(const KpArgs &a, const int m, const int npos) {
+    if (__lane_id() == 0) a.cnt[m] = kp_count(npos);
+}
+
+// What a global-store kernel leaves of query m: its rows in the form a.planes_lo asks for and, from the wave with `first`, the count.
+template <int VEC, int NCH, bool CHECK_C>
+__device__ __forceinline__ void kp_store(const KpArgs &a, const int m, const int c0, const f32x4 (&acc)[NCH][VEC], const int npos, const bool first) {
+    if (a.planes_lo)
+        kp_store_rows<VEC, NCH, CHECK_C, true>(a, m, c0, acc);
+    else
+        kp_store_rows<VEC, NCH, CHECK_C, false>(a, m, c0, acc);
+    if (first) kp_store_cnt(a, m, npos);
 }
 
 // amdgpu_waves_per_eu: the occupancy each form had before the step loop got its wave-uniform branches - left alone, the register
@@ -240,73 +347,16 @@ __device__ __forceinline__ void kp_aggregate_query(KpArgs a, const int m, const 
 template <int VEC, int NCH, bool REC>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(VEC * NCH == 8 ? 4 : (VEC * NCH == 4 ? 6 : 8)))) void kpconv_aggregate_kernel(KpArgs a) {
     __shared__ float4 rec_s[4][KP_PHASE_DEFAULT + KP_PAD];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int wv = threadIdx.x >> 6;
     // the query id is wave-uniform: keep it (and everything derived from it) in scalar registers
     int m = __builtin_amdgcn_readfirstlane(xcd_contiguous_block(blockIdx.x, gridDim.x) * 4 + wv);
     if (m >= a.M) return;
     if (a.order) m = (m / a.Mpf) * a.Mpf + a.order[m];
-    const int j = lane & 15, g = lane >> 4;
     const int c0 = blockIdx.y * (16 * VEC * NCH);
     f32x4 acc[NCH][VEC];
     int npos;
     kp_aggregate_query<VEC, NCH, KP_PHASE_DEFAULT, REC>(a, m, c0, rec_s[wv], acc, npos);
-    // D layout 16x16: row (kernel point) = 4*g + r, col = j  ->  channels c .. c+VEC-1 contiguous
-    if (a.planes_lo) {   // bf16 hi / lo planes (same rounding as the GEMM's on-the-fly split: identical products)
-        uint16_t *hrow = reinterpret_cast<uint16_t *>(a.agg) + (size_t)m * a.ld_agg;
-#pragma unroll
-        for (int ch = 0; ch < NCH; ++ch) {
-            const int c = c0 + ch * 16 * VEC + VEC * j;
-            if (c < a.C) {
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int k = 4 * g + r;
-                    if (k < 15) {
-                        uint16_t *dst = hrow + (size_t)k * a.C + c;
-                        if constexpr (VEC == 4) {
-                            uint2 hi, lo;
-                            cofi_split2(acc[ch][0][r], acc[ch][1][r], hi.x, lo.x);
-                            cofi_split2(acc[ch][2][r], acc[ch][3][r], hi.y, lo.y);
-                            *reinterpret_cast<uint2 *>(dst) = hi;
-                            *reinterpret_cast<uint2 *>(dst + a.planes_lo) = lo;
-                        } else if constexpr (VEC == 2) {
-                            unsigned hi, lo;
-                            cofi_split2(acc[ch][0][r], acc[ch][1][r], hi, lo);
-                            *reinterpret_cast<unsigned *>(dst) = hi;
-                            *reinterpret_cast<unsigned *>(dst + a.planes_lo) = lo;
-                        } else {
-                            unsigned hi, lo;
-                            cofi_split2(acc[ch][0][r], 0.f, hi, lo);
-                            dst[0] = (uint16_t)hi;
-                            dst[a.planes_lo] = (uint16_t)lo;
-                        }
-                    }
-                }
-            }
-        }
-        if (blockIdx.y == 0 && lane == 0) a.cnt[m] = (float)(npos > 1 ? npos : 1);
-        return;
-    }
-    float *orow = a.agg + (size_t)m * a.ld_agg;
-#pragma unroll
-    for (int ch = 0; ch < NCH; ++ch) {
-        const int c = c0 + ch * 16 * VEC + VEC * j;
-        if (c < a.C) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int k = 4 * g + r;
-                if (k < 15) {
-                    float *dst = orow + (size_t)k * a.C + c;
-                    if constexpr (VEC == 4)
-                        *reinterpret_cast<float4 *>(dst) = make_float4(acc[ch][0][r], acc[ch][1][r], acc[ch][2][r], acc[ch][3][r]);
-                    else if constexpr (VEC == 2)
-                        *reinterpret_cast<float2 *>(dst) = make_float2(acc[ch][0][r], acc[ch][1][r]);
-                    else
-                        dst[0] = acc[ch][0][r];
-                }
-            }
-        }
-    }
-    if (blockIdx.y == 0 && lane == 0) a.cnt[m] = (float)(npos > 1 ? npos : 1);
+    kp_store<VEC, NCH, true>(a, m, c0, acc, npos, blockIdx.y == 0);
 }
 
 // Wide layers (C = 256 / 512: NP = C / 128 channel passes) with few queries (1280 ... 2560 at the deep stages): the NP passes of a
@@ -323,65 +373,35 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5))) void k
     const int j = lane & 15;
     int m = __builtin_amdgcn_readfirstlane(xcd_contiguous_block(blockIdx.x, gridDim.x) * QW + qs);   // host: M % QW == 0
     if (a.order) m = (m / a.Mpf) * a.Mpf + a.order[m];
-    {
-        const size_t fo = (size_t)(m / a.Mpf) * a.N;
-        a.feats += fo * a.ldf;
-        if constexpr (REC) {
-            a.recs += fo;
-        } else {
-            a.s_pts += fo * 3;
-            a.row_pos += fo;
-        }
-    }
-    const float qx = a.q_pts[3 * m], qy = a.q_pts[3 * m + 1], qz = a.q_pts[3 * m + 2];
-    const int jk = j < 15 ? j : 0;
-    const float kx = a.kp[3 * jk], ky = a.kp[3 * jk + 1], kz = a.kp[3 * jk + 2];
-    const float inv_sigma = 1.0f / a.sigma;
-    float rsup;
-    {
-        float kn = j < 15 ? __builtin_amdgcn_sqrtf((kx * kx + ky * ky) + kz * kz) : 0.f;
-#pragma unroll
-        for (int o = 8; o > 0; o >>= 1) kn = fmaxf(kn, __shfl_xor(kn, o, 64));
-        rsup = (kn + a.sigma) * 1.00002f;
-    }
-    const float rsup2 = rsup * rsup;
+    kp_shift_frame<REC>(a, m);
+    const KpQuery q = kp_query(a, m, j);
     // ---- this wave's share of the staging: neighbours [p * SH, (p + 1) * SH), lane = neighbour
     const int hl = p * SH + lane;
     const bool mine = lane < SH && hl < a.H;
     const int id = mine ? a.idx[(size_t)m * a.H + hl] : a.N;
     const bool valid = (unsigned)id < (unsigned)a.N;
-    const int idc = valid ? id : 0;
     float px, py, pz;
     int rp;
-    if constexpr (REC) {
-        const float4 rv = a.recs[idc];
-        px = rv.x; py = rv.y; pz = rv.z;
-        rp = rv.w != 0.f;
-    } else {
-        const float *sp = a.s_pts + 3 * (size_t)idc;
-        px = sp[0]; py = sp[1]; pz = sp[2];
-        rp = a.row_pos[idc];
-    }
-    const float dx = px - qx, dy = py - qy, dz = pz - qz;
-    const bool inside = valid && (dx * dx + dy * dy) + dz * dz < rsup2;
-    const unsigned long long msk = __ballot(inside);
-    const int npos_w = __popcll(__ballot(valid && rp != 0));
-    if (lane == 0) { cnt_s[qs][p] = __popcll(msk); pos_s[qs][p] = npos_w; }
+    kp_support<REC>(a, valid ? id : 0, px, py, pz, rp);
+    const float dx = px - q.qx, dy = py - q.qy, dz = pz - q.qz;
+    const bool inside = valid && (dx * dx + dy * dy) + dz * dz < q.rsup2;
+    const int nin_w = __popcll(__ballot(inside)), npos_w = __popcll(__ballot(valid && rp != 0));
+    if (lane == 0) { cnt_s[qs][p] = nin_w; pos_s[qs][p] = npos_w; }
     __syncthreads();
     int off = 0, nin = 0, npos = 0;
 #pragma unroll
-    for (int q = 0; q < NP; ++q) {
-        const int c = cnt_s[qs][q];
-        off += q < p ? c : 0;
+    for (int w = 0; w < NP; ++w) {
+        const int c = cnt_s[qs][w];
+        off += w < p ? c : 0;
         nin += c;
-        npos += pos_s[qs][q];
+        npos += pos_s[qs][w];
     }
     // wave-uniform, but read from LDS: into scalar registers, so that the step loop's tests on nin are scalar branches
     nin = __builtin_amdgcn_readfirstlane(nin);
     npos = __builtin_amdgcn_readfirstlane(npos);
     float4 *rec = rec_s[qs];
-    if (inside) rec[off + __popcll(msk & ((1ull << lane) - 1ull))] = make_float4(dx, dy, dz, __int_as_float(id));
-    if (p == 0) rec[nin + lane] = make_float4(1e18f, 0.f, 0.f, __int_as_float(0));   // shadow records behind the list
+    kp_compact(rec, off, inside, make_float4(dx, dy, dz, __int_as_float(id)));   // behind the survivors of the waves before this one
+    if (p == 0) kp_shadow(rec, nin);
     __syncthreads();
     // ---- this wave's channel pass over the shared records
     const int c0 = p * (16 * VEC * NCH);
@@ -393,42 +413,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5))) void k
     for (int ch = 0; ch < NCH; ++ch)
 #pragma unroll
         for (int v = 0; v < VEC; ++v) acc[ch][v] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    kp_steps<VEC, NCH>(reinterpret_cast<const char *>(a.feats), 4u * a.ldf, coffb, rec, nin, kx, ky, kz, inv_sigma, acc);
-    // the store addresses are derived from a lane id taken AFTER the step loop, so that nothing of them occupies registers across it
-    const int ls = __lane_id(), js = ls & 15, g = ls >> 4;
-    if (a.planes_lo) {   // bf16 hi / lo planes, as kpconv_aggregate_kernel writes them
-        uint16_t *hrow = reinterpret_cast<uint16_t *>(a.agg) + (size_t)m * a.ld_agg;
-#pragma unroll
-        for (int ch = 0; ch < NCH; ++ch) {
-            const int c = c0 + ch * 16 * VEC + VEC * js;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int k = 4 * g + r;
-                if (k < 15) {
-                    uint16_t *dst = hrow + (size_t)k * a.C + c;
-                    uint2 hi, lo;
-                    cofi_split2(acc[ch][0][r], acc[ch][1][r], hi.x, lo.x);
-                    cofi_split2(acc[ch][2][r], acc[ch][3][r], hi.y, lo.y);
-                    *reinterpret_cast<uint2 *>(dst) = hi;
-                    *reinterpret_cast<uint2 *>(dst + a.planes_lo) = lo;
-                }
-            }
-        }
-        if (p == 0 && ls == 0) a.cnt[m] = (float)(npos > 1 ? npos : 1);
-        return;
-    }
-    float *orow = a.agg + (size_t)m * a.ld_agg;
-#pragma unroll
-    for (int ch = 0; ch < NCH; ++ch) {
-        const int c = c0 + ch * 16 * VEC + VEC * js;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int k = 4 * g + r;
-            if (k < 15)
-                *reinterpret_cast<float4 *>(orow + (size_t)k * a.C + c) = make_float4(acc[ch][0][r], acc[ch][1][r], acc[ch][2][r], acc[ch][3][r]);
-        }
-    }
-    if (p == 0 && ls == 0) a.cnt[m] = (float)(npos > 1 ? npos : 1);
+    kp_steps<VEC, NCH>(reinterpret_cast<const char *>(a.feats), 4u * a.ldf, coffb, rec, nin, q.kx, q.ky, q.kz, q.inv_sigma, acc);
+    kp_store<VEC, NCH, false>(a, m, c0, acc, npos, p == 0);
 }
 
 // C <= 4 (the first layer of the encoder: [intensity | normal]).  What a neighbour costs in the staging is the number of distinct
@@ -456,18 +442,7 @@ __global__ __launch_bounds__(256) void kpconv_aggregate_c4_kernel(KpArgs a) {   
     if (a.order) m = (m / a.Mpf) * a.Mpf + a.order[m];
     const int j = lane & 15, g = lane >> 4;
     const float4 *recs = reinterpret_cast<const float4 *>(a.feats) + 2 * (size_t)(m / a.Mpf) * a.N;   // stack mode: this query's frame
-    const float qx = a.q_pts[3 * m], qy = a.q_pts[3 * m + 1], qz = a.q_pts[3 * m + 2];
-    const int jk = j < 15 ? j : 0;
-    const float kx = a.kp[3 * jk], ky = a.kp[3 * jk + 1], kz = a.kp[3 * jk + 2];
-    const float inv_sigma = 1.0f / a.sigma;
-    float rsup;   // support of the kernel, as in kp_aggregate_query: same neighbours kept, same order -> identical bits
-    {
-        float kn = j < 15 ? __builtin_amdgcn_sqrtf((kx * kx + ky * ky) + kz * kz) : 0.f;
-#pragma unroll
-        for (int o = 8; o > 0; o >>= 1) kn = fmaxf(kn, __shfl_xor(kn, o, 64));
-        rsup = (kn + a.sigma) * 1.00002f;
-    }
-    const float rsup2 = rsup * rsup;
+    const KpQuery q = kp_query(a, m, j);   // the support of kp_aggregate_query: same neighbours kept, same order -> identical bits
     f32x4 acc = {0.f, 0.f, 0.f, 0.f};
     int npos = 0;
     const int32_t *irow = a.idx + (size_t)m * a.H;
@@ -494,8 +469,9 @@ __global__ __launch_bounds__(256) void kpconv_aggregate_c4_kernel(KpArgs a) {   
         for (int r = 0; r < 2; ++r) {
             const bool valid = (unsigned)idr[r] < (unsigned)a.N;
             npos += __popcll(__ballot(valid && pp[r].w != 0.f));
-            const float dx = pp[r].x - qx, dy = pp[r].y - qy, dz = pp[r].z - qz;
-            const bool inside = valid && (dx * dx + dy * dy) + dz * dz < rsup2;
+            const float dx = pp[r].x - q.qx, dy = pp[r].y - q.qy, dz = pp[r].z - q.qz;
+            const bool inside = valid && (dx * dx + dy * dy) + dz * dz < q.rsup2;
+            // kp_compact writes one array; two calls cost this kernel registers and instructions, so its two-array compaction stays here
             const unsigned long long msk = __ballot(inside);
             if (inside) {
                 const int slot = nin + __popcll(msk & ((1ull << lane) - 1ull));
@@ -513,14 +489,14 @@ __global__ __launch_bounds__(256) void kpconv_aggregate_c4_kernel(KpArgs a) {   
         for (int t = 0; t < steps; ++t) {
             const float4 rc = rec[4 * t + g];
             const float f = fsel[(4 * t + g) * 4] * fmask;
-            const float dx = rc.x - kx, dy = rc.y - ky, dz = rc.z - kz;
+            const float dx = rc.x - q.kx, dy = rc.y - q.ky, dz = rc.z - q.kz;
             const float sq = (dx * dx + dy * dy) + dz * dz;
-            const float w = fmaxf(1.0f - __builtin_amdgcn_sqrtf(sq) * inv_sigma, 0.0f);
+            const float w = fmaxf(1.0f - __builtin_amdgcn_sqrtf(sq) * q.inv_sigma, 0.0f);
             acc = __builtin_amdgcn_mfma_f32_16x16x4f32(w, f, acc, 0, 0, 0);
         }
         __builtin_amdgcn_wave_barrier();
     }
-    if (j < a.C) {
+    if (j < a.C) {   // MFMA column j = channel j
         float *orow = a.agg + (size_t)m * a.ld_agg;
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
@@ -528,7 +504,7 @@ __global__ __launch_bounds__(256) void kpconv_aggregate_c4_kernel(KpArgs a) {   
             if (k < 15) orow[(size_t)k * a.C + j] = acc[r];
         }
     }
-    if (lane == 0) a.cnt[m] = (float)(npos > 1 ? npos : 1);
+    kp_store_cnt(a, m, npos);
 }
 
 // ---- KPConv as ONE kernel for the narrow layers (mid = 32 / 64 channels: the stages with 20 480 ... 5 120 queries) ----------------
@@ -606,22 +582,11 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
                 const int k = 4 * g + r;
                 if (k < 15) {
                     const int off = ql * KLD + k * MID + VEC * j;
-                    if constexpr (VEC == 4) {
-                        uint2 hi, lo;
-                        cofi_split2(acc[0][0][r], acc[0][1][r], hi.x, lo.x);
-                        cofi_split2(acc[0][2][r], acc[0][3][r], hi.y, lo.y);
-                        *reinterpret_cast<uint2 *>(t_hi + off) = hi;
-                        *reinterpret_cast<uint2 *>(t_lo + off) = lo;
-                    } else {
-                        unsigned hi, lo;
-                        cofi_split2(acc[0][0][r], acc[0][1][r], hi, lo);
-                        *reinterpret_cast<unsigned *>(t_hi + off) = hi;
-                        *reinterpret_cast<unsigned *>(t_lo + off) = lo;
-                    }
+                    kp_split_store<VEC>(acc[0], r, t_hi + off, t_lo + off);
                 }
             }
             if (lane == 0) {
-                cnt_s[ql] = (float)(npos > 1 ? npos : 1);
+                cnt_s[ql] = kp_count(npos);
                 m_s[ql] = m;
             }
         }
@@ -810,18 +775,34 @@ extern "C" int cofi_kp_pack_support(const float *feats, int ldf, int N, int C, c
     return cofi_launch_status();
 }
 
+// The operands every aggregation kernel takes, under the entry points' own names (M, N: rows per frame).  The support is s_pts + row_pos,
+// or records, or neither (first-layer form: feats are the packed records); the fused kernel has no agg / cnt.
+static KpArgs kp_args(const float *feats, int ldf, int N, int C, const float *q_pts, const float *s_pts, const uint8_t *row_pos, const float *records,
+                      const int32_t *idx, int M, int H, const float *kernel_points, float sigma, float *agg, int ld_agg, int agg_planes, float *cnt,
+                      int frames, const int32_t *order) {
+    KpArgs a{};
+    a.feats = feats; a.ldf = ldf; a.N = N; a.C = C;
+    a.q_pts = q_pts; a.s_pts = s_pts; a.row_pos = row_pos; a.recs = (const float4 *)records;
+    a.idx = idx; a.M = M * frames; a.Mpf = M; a.H = H;
+    a.kp = kernel_points; a.sigma = sigma;
+    a.agg = agg; a.ld_agg = ld_agg; a.planes_lo = agg_planes ? (size_t)M * frames * ld_agg : 0; a.cnt = cnt;
+    a.order = order;
+    return a;
+}
+
+// kp_steps forms a feature row's byte offset with one 24 x 24-bit multiply: row ids and 4 ldf below 2^24, the frame's features below 4 GiB
+static int kp_check_support(int N, int ldf) {
+    return ((size_t)N * ldf * 4 >= ((size_t)1 << 32) || N >= (1 << 24) || (size_t)ldf * 4 >= (1u << 24)) ? COFI_EUNSUPPORTED : 0;
+}
+
 // Shape checks and kernel choice of the aggregation; REC: the support arrives as 16-byte records (a.recs) instead of a.s_pts / a.row_pos.
 template <bool REC>
-static int kp_aggregate_launch(KpArgs a, int M, int agg_planes, int frames, cofi_stream_t stream) {
-    const int N = a.N, C = a.C, H = a.H, ldf = a.ldf, ld_agg = a.ld_agg;
-    if (N <= 0 || C <= 0 || M < 0 || H <= 0 || (H & 3) || ldf < C || ld_agg < 15 * C || !(a.sigma > 0.f) || frames <= 0) return COFI_EINVAL;
+static int kp_aggregate_launch(const KpArgs &a, int agg_planes, int frames, cofi_stream_t stream) {
+    const int N = a.N, C = a.C, M = a.M, H = a.H, ldf = a.ldf, ld_agg = a.ld_agg;   // M: the queries of all frames
+    if (N <= 0 || C <= 0 || a.Mpf < 0 || H <= 0 || (H & 3) || ldf < C || ld_agg < 15 * C || !(a.sigma > 0.f) || frames <= 0) return COFI_EINVAL;
     if (agg_planes && ((ld_agg & 7) || (C & 3) || ((uintptr_t)a.agg & 15))) return COFI_EINVAL;
-    if ((size_t)N * ldf * 4 >= ((size_t)1 << 32) || N >= (1 << 24) || (size_t)ldf * 4 >= (1u << 24)) return COFI_EUNSUPPORTED;  // 24x24-bit row offsets
+    if (int rc = kp_check_support(N, ldf)) return rc;
     if (M == 0) return 0;
-    a.M = M * frames;
-    a.Mpf = M;
-    a.planes_lo = agg_planes ? (size_t)M * frames * ld_agg : 0;
-    M *= frames;
     hipStream_t s = cofi_s(stream);
     const int mb = cofi_cdiv(M, 4);
     if ((C == 256 || C == 512) && (ldf & 3) == 0 && H <= 128 && M % (C == 256 ? 2 : 1) == 0) {
@@ -847,8 +828,8 @@ extern "C" int cofi_kpconv_aggregate(const float *feats, int ldf, int N, int C, 
                                      const uint8_t *row_pos, float *agg, int ld_agg, int agg_planes, float *cnt, int frames, const int32_t *order,
                                      cofi_stream_t stream) {
     if (!feats || !q_pts || !s_pts || !idx || !kernel_points || !row_pos || !agg || !cnt) return COFI_EINVAL;
-    KpArgs a{feats, q_pts, s_pts, kernel_points, idx, row_pos, agg, cnt, ldf, N, C, 0, H, ld_agg, sigma, 0, 0, order, nullptr};
-    return kp_aggregate_launch<false>(a, M, agg_planes, frames, stream);
+    return kp_aggregate_launch<false>(kp_args(feats, ldf, N, C, q_pts, s_pts, row_pos, nullptr, idx, M, H, kernel_points, sigma, agg, ld_agg, agg_planes,
+                                              cnt, frames, order), agg_planes, frames, stream);
 }
 
 // cofi_kpconv_aggregate with the support as 16-byte records (x, y, z, flag) - (frames * N, 4) floats, written by the GroupNorm apply
@@ -857,8 +838,8 @@ extern "C" int cofi_kpconv_aggregate_rec(const float *feats, int ldf, int N, int
                                          const int32_t *idx, int M, int H, const float *kernel_points, float sigma, float *agg, int ld_agg,
                                          int agg_planes, float *cnt, int frames, const int32_t *order, cofi_stream_t stream) {
     if (!feats || !q_pts || !records || !idx || !kernel_points || !agg || !cnt || ((uintptr_t)records & 15)) return COFI_EINVAL;
-    KpArgs a{feats, q_pts, nullptr, kernel_points, idx, nullptr, agg, cnt, ldf, N, C, 0, H, ld_agg, sigma, 0, 0, order, (const float4 *)records};
-    return kp_aggregate_launch<true>(a, M, agg_planes, frames, stream);
+    return kp_aggregate_launch<true>(kp_args(feats, ldf, N, C, q_pts, nullptr, nullptr, records, idx, M, H, kernel_points, sigma, agg, ld_agg, agg_planes,
+                                             cnt, frames, order), agg_planes, frames, stream);
 }
 
 // First-layer form (C <= 4): pack [features | position | positive-sum flag] into 32-byte records once, then aggregate from them.
@@ -874,7 +855,7 @@ extern "C" int cofi_kpconv_aggregate_c4(const float *records, int N, int C, cons
     if (!records || !q_pts || !idx || !kernel_points || !agg || !cnt || ((uintptr_t)records & 15)) return COFI_EINVAL;
     if (N <= 0 || C <= 0 || C > 4 || M < 0 || H <= 0 || (H & 3) || ld_agg < 15 * C || !(sigma > 0.f) || frames <= 0) return COFI_EINVAL;
     if (M == 0) return 0;
-    KpArgs a{records, q_pts, nullptr, kernel_points, idx, nullptr, agg, cnt, 8, N, C, M * frames, H, ld_agg, sigma, M, 0, order};
+    const KpArgs a = kp_args(records, 8, N, C, q_pts, nullptr, nullptr, nullptr, idx, M, H, kernel_points, sigma, agg, ld_agg, 0, cnt, frames, order);
     hipLaunchKernelGGL(kpconv_aggregate_c4_kernel, dim3(cofi_cdiv((long)M * frames, 4)), dim3(256), 0, cofi_s(stream), a);
     return cofi_launch_status();
 }
@@ -889,22 +870,21 @@ extern "C" int cofi_kpconv_fused_slab_rows(int C, int M, int frames) {
 }
 
 template <bool REC>
-static int kp_fused_launch(const float *feats, int ldf, int N, int C, const float *q_pts, const float *s_pts, const float4 *recs, const int32_t *idx,
-                           int M, int H, const float *kernel_points, float sigma, const uint8_t *row_pos, const void *w_planes, int ldw,
-                           const float *bias, float *y, int ldy, float *colpart, int stat_width, int frames, const int32_t *order,
-                           cofi_stream_t stream) {
-    if (N <= 0 || M <= 0 || H <= 0 || (H & 3) || ldf < C || ldy < C || !(sigma > 0.f) || frames <= 0) return COFI_EINVAL;
+static int kp_fused_launch(const KpArgs &a, const void *w_planes, int ldw, const float *bias, float *y, int ldy, float *colpart, int stat_width,
+                           int frames, cofi_stream_t stream) {
+    const int N = a.N, C = a.C, M = a.Mpf, ldf = a.ldf;
+    if (N <= 0 || M <= 0 || a.H <= 0 || (a.H & 3) || ldf < C || ldy < C || !(a.sigma > 0.f) || frames <= 0) return COFI_EINVAL;
     if (ldw < 15 * C || (ldw & 7) || ((uintptr_t)w_planes & 15)) return COFI_EINVAL;
     const int qt = cofi_kpconv_fused_slab_rows(C, M, frames);
     if (qt == 0 || (ldf & (C / 16 - 1))) return COFI_EUNSUPPORTED;
-    if ((size_t)N * ldf * 4 >= ((size_t)1 << 32) || N >= (1 << 24) || (size_t)ldf * 4 >= (1u << 24)) return COFI_EUNSUPPORTED;  // 24x24-bit row offsets
+    if (int rc = kp_check_support(N, ldf)) return rc;
     int shift = 0;
     if (colpart) {
         if (stat_width <= 0 || (stat_width & (stat_width - 1)) || stat_width > 16 || (C % stat_width)) return COFI_EINVAL;
         while ((1 << shift) < stat_width) ++shift;
     }
     KpFusedArgs fa{};
-    fa.a = KpArgs{feats, q_pts, s_pts, kernel_points, idx, row_pos, nullptr, nullptr, ldf, N, C, M * frames, H, 0, sigma, M, 0, order, recs};
+    fa.a = a;
     fa.w_hi = (const uint16_t *)w_planes;
     fa.w_lo = fa.w_hi + (size_t)C * ldw;
     fa.ldw = ldw; fa.bias = bias; fa.y = y; fa.ldy = ldy; fa.colpart = colpart; fa.stat_shift = shift; fa.qt = qt;
@@ -920,8 +900,8 @@ extern "C" int cofi_kpconv_fused(const float *feats, int ldf, int N, int C, cons
                                  const float *kernel_points, float sigma, const uint8_t *row_pos, const void *w_planes, int ldw, const float *bias,
                                  float *y, int ldy, float *colpart, int stat_width, int frames, const int32_t *order, cofi_stream_t stream) {
     if (!feats || !q_pts || !s_pts || !idx || !kernel_points || !row_pos || !w_planes || !y) return COFI_EINVAL;
-    return kp_fused_launch<false>(feats, ldf, N, C, q_pts, s_pts, nullptr, idx, M, H, kernel_points, sigma, row_pos, w_planes, ldw, bias, y, ldy,
-                                  colpart, stat_width, frames, order, stream);
+    return kp_fused_launch<false>(kp_args(feats, ldf, N, C, q_pts, s_pts, row_pos, nullptr, idx, M, H, kernel_points, sigma, nullptr, 0, 0, nullptr, frames,
+                                          order), w_planes, ldw, bias, y, ldy, colpart, stat_width, frames, stream);
 }
 
 // cofi_kpconv_fused with the support as 16-byte records (see cofi_kpconv_aggregate_rec)
@@ -929,8 +909,8 @@ extern "C" int cofi_kpconv_fused_rec(const float *feats, int ldf, int N, int C, 
                                      int H, const float *kernel_points, float sigma, const void *w_planes, int ldw, const float *bias, float *y,
                                      int ldy, float *colpart, int stat_width, int frames, const int32_t *order, cofi_stream_t stream) {
     if (!feats || !q_pts || !records || !idx || !kernel_points || !w_planes || !y || ((uintptr_t)records & 15)) return COFI_EINVAL;
-    return kp_fused_launch<true>(feats, ldf, N, C, q_pts, nullptr, (const float4 *)records, idx, M, H, kernel_points, sigma, nullptr, w_planes, ldw,
-                                 bias, y, ldy, colpart, stat_width, frames, order, stream);
+    return kp_fused_launch<true>(kp_args(feats, ldf, N, C, q_pts, nullptr, nullptr, records, idx, M, H, kernel_points, sigma, nullptr, 0, 0, nullptr, frames,
+                                         order), w_planes, ldw, bias, y, ldy, colpart, stat_width, frames, stream);
 }
 
 extern "C" int cofi_neighbor_maxpool(const float *x, int ldx, int N, int C, const int32_t *idx, int M, int H, float *out, int ldo,

@@ -609,44 +609,60 @@ def row_sum_positive(feats: torch.Tensor) -> torch.Tensor:
     return out
 
 
+def _kp_operands(what: str, feats, q_pts, s_pts, idx, kernel_points, frames: int):
+    """The operand checks of the KPConv operators -> N, C, M, H (rows of all frames)."""
+    _mat(feats, "feats"), _mat(idx, "idx", torch.int32)
+    if not (q_pts.is_contiguous() and s_pts.is_contiguous() and kernel_points.is_contiguous() and idx.is_contiguous()):
+        raise _lib.CofiError("%s: points / idx / kernel_points must be contiguous" % what)
+    N, C = feats.shape
+    M, H = idx.shape
+    if s_pts.shape != (N, 3) or q_pts.shape != (M, 3) or kernel_points.shape != (15, 3) or N % frames or M % frames:
+        raise _lib.CofiError("%s: shape mismatch" % what)
+    return N, C, M, H
+
+
+def _kp_row_pos(feats, row_pos):
+    """The caller's row_pos, else the one the group_norm_apply that produced `feats` left on it, else None."""
+    return getattr(feats, "cofi_row_pos", None) if row_pos is None else row_pos
+
+
+def _kp_support(feats, s_pts, row_pos):
+    """Where the aggregation takes positions and positive-sum flags of the support from -> ("rec", records (N, 4)) or ("rows", row_pos):
+    the caller's or the attached row_pos, else records (attached or packed now), else - COFI_KPCONV_RECORDS=0 - row_sum_positive."""
+    row_pos = _kp_row_pos(feats, row_pos)
+    if row_pos is not None:
+        return "rows", row_pos
+    if kpconv_records():
+        return "rec", _support_records(feats, s_pts)
+    return "rows", row_sum_positive(feats)
+
+
 def kpconv_aggregate(feats, q_pts, s_pts, idx, kernel_points, sigma: float, row_pos=None, frames: int = 1, order=None, planes: bool = False):
     """-> agg (M, 15*C), cnt (M,) float.  idx int32 (M,H).  Stack mode: `frames` equally sized frames stacked along
     the rows of every argument, idx frame-local."""
     lib = _lib.load()
-    _mat(feats, "feats"), _mat(idx, "idx", torch.int32)
-    if not (q_pts.is_contiguous() and s_pts.is_contiguous() and kernel_points.is_contiguous() and idx.is_contiguous()):
-        raise _lib.CofiError("kpconv_aggregate: points / idx / kernel_points must be contiguous")
-    N, C = feats.shape
-    M, H = idx.shape
-    if s_pts.shape != (N, 3) or q_pts.shape != (M, 3) or kernel_points.shape != (15, 3) or N % frames or M % frames:
-        raise _lib.CofiError("kpconv_aggregate: shape mismatch")
-    if row_pos is None:
-        row_pos = getattr(feats, "cofi_row_pos", None)   # left there by the group_norm_apply that produced feats
+    N, C, M, H = _kp_operands("kpconv_aggregate", feats, q_pts, s_pts, idx, kernel_points, frames)
     planes = planes and C % 4 == 0 and C > 4 and (15 * C) % 8 == 0
     if planes:   # bf16 hi / lo planes: the part-2 GEMM takes them without any conversion (SplitA)
         agg = torch.empty((2, M, 15 * C), dtype=torch.int16, device=feats.device)
     else:
         agg = torch.empty((M, 15 * C), dtype=torch.float32, device=feats.device)
     cnt = torch.empty((M,), dtype=torch.float32, device=feats.device)
-    if C <= 4 and row_pos is None and M > 0:
+    tail = (_p(idx), M // frames, H, _p(kernel_points), float(sigma))
+    if C <= 4 and _kp_row_pos(feats, row_pos) is None and M > 0:
         # first layer: [features | position | positive-sum flag] packed into 32-byte records, one gather per neighbour
         recs = torch.empty((N, 8), dtype=torch.float32, device=feats.device)
         _lib.check(lib.cofi_kp_pack_c4(_p(feats), _ld(feats), C, _p(s_pts), N, _p(recs), _stream()), "cofi_kp_pack_c4")
-        rc = lib.cofi_kpconv_aggregate_c4(_p(recs), N // frames, C, _p(q_pts), _p(idx), M // frames, H, _p(kernel_points), float(sigma), _p(agg),
-                                          15 * C, _p(cnt), frames, _p(order), _stream())
+        rc = lib.cofi_kpconv_aggregate_c4(_p(recs), N // frames, C, _p(q_pts), *tail, _p(agg), 15 * C, _p(cnt), frames, _p(order), _stream())
         _lib.check(rc, "cofi_kpconv_aggregate_c4")
         return agg, cnt
-    if row_pos is None and kpconv_records():
-        recs = _support_records(feats, s_pts)
-        rc = lib.cofi_kpconv_aggregate_rec(_p(feats), _ld(feats), N // frames, C, _p(q_pts), _p(recs), _p(idx), M // frames, H, _p(kernel_points),
-                                           float(sigma), _p(agg), 15 * C, int(planes), _p(cnt), frames, _p(order), _stream())
-        _lib.check(rc, "cofi_kpconv_aggregate_rec")
-        return (SplitA(agg, 15 * C) if planes else agg), cnt
-    if row_pos is None:
-        row_pos = row_sum_positive(feats)
-    rc = lib.cofi_kpconv_aggregate(_p(feats), _ld(feats), N // frames, C, _p(q_pts), _p(s_pts), _p(idx), M // frames, H,
-                                   _p(kernel_points), float(sigma), _p(row_pos), _p(agg), 15 * C, int(planes), _p(cnt), frames, _p(order), _stream())
-    _lib.check(rc, "cofi_kpconv_aggregate")
+    head = (_p(feats), _ld(feats), N // frames, C, _p(q_pts))
+    out = (_p(agg), 15 * C, int(planes), _p(cnt), frames, _p(order), _stream())
+    kind, sup = _kp_support(feats, s_pts, row_pos)
+    if kind == "rec":
+        _lib.check(lib.cofi_kpconv_aggregate_rec(*head, _p(sup), *tail, *out), "cofi_kpconv_aggregate_rec")
+    else:
+        _lib.check(lib.cofi_kpconv_aggregate(*head, _p(s_pts), *tail, _p(sup), *out), "cofi_kpconv_aggregate")
     return (SplitA(agg, 15 * C) if planes else agg), cnt
 
 
@@ -662,33 +678,22 @@ def kpconv_fused(feats, q_pts, s_pts, idx, kernel_points, sigma: float, w: "Spli
     """The whole KPConv operator (kpconv.py:91-116) of a narrow layer (C = 32 / 64 in = out channels) in one launch: -> (y (M, C),
     statistics partials (M / slab_rows, C / stat_width, 2), slab_rows).  `w`: the (C, 15 C) packed weight as pre-split planes."""
     lib = _lib.load()
-    _mat(feats, "feats"), _mat(idx, "idx", torch.int32)
-    if not (q_pts.is_contiguous() and s_pts.is_contiguous() and kernel_points.is_contiguous() and idx.is_contiguous()):
-        raise _lib.CofiError("kpconv_fused: points / idx / kernel_points must be contiguous")
-    N, C = feats.shape
-    M, H = idx.shape
-    if s_pts.shape != (N, 3) or q_pts.shape != (M, 3) or kernel_points.shape != (15, 3) or N % frames or M % frames:
-        raise _lib.CofiError("kpconv_fused: shape mismatch")
+    N, C, M, H = _kp_operands("kpconv_fused", feats, q_pts, s_pts, idx, kernel_points, frames)
     if not isinstance(w, SplitW) or tuple(w.shape) != (C, 15 * C):
         raise _lib.CofiError("kpconv_fused: the weight must be the pre-split (C, 15 C) packing")
     sr = kpconv_fused_slab_rows(C, M // frames, frames)
     if sr == 0:
         raise _lib.CofiError("kpconv_fused: shape not supported (C in {32, 64}, M % 16 == 0, bf16x3 arithmetic)")
-    if row_pos is None:
-        row_pos = getattr(feats, "cofi_row_pos", None)   # left there by the group_norm_apply that produced feats
     y = torch.empty((M, C), dtype=torch.float32, device=feats.device)
     part = torch.empty((M // sr, C // stat_width, 2), dtype=torch.float32, device=feats.device)
-    if row_pos is None and kpconv_records():
-        recs = _support_records(feats, s_pts)
-        rc = lib.cofi_kpconv_fused_rec(_p(feats), _ld(feats), N // frames, C, _p(q_pts), _p(recs), _p(idx), M // frames, H, _p(kernel_points),
-                                       float(sigma), _p(w.planes), w.ldp, _p(bias), _p(y), _ld(y), _p(part), stat_width, frames, _p(order), _stream())
-        _lib.check(rc, "cofi_kpconv_fused_rec")
-        return y, part, sr
-    if row_pos is None:
-        row_pos = row_sum_positive(feats)
-    rc = lib.cofi_kpconv_fused(_p(feats), _ld(feats), N // frames, C, _p(q_pts), _p(s_pts), _p(idx), M // frames, H, _p(kernel_points), float(sigma),
-                               _p(row_pos), _p(w.planes), w.ldp, _p(bias), _p(y), _ld(y), _p(part), stat_width, frames, _p(order), _stream())
-    _lib.check(rc, "cofi_kpconv_fused")
+    head = (_p(feats), _ld(feats), N // frames, C, _p(q_pts))
+    tail = (_p(idx), M // frames, H, _p(kernel_points), float(sigma))
+    out = (_p(w.planes), w.ldp, _p(bias), _p(y), _ld(y), _p(part), stat_width, frames, _p(order), _stream())
+    kind, sup = _kp_support(feats, s_pts, row_pos)
+    if kind == "rec":
+        _lib.check(lib.cofi_kpconv_fused_rec(*head, _p(sup), *tail, *out), "cofi_kpconv_fused_rec")
+    else:
+        _lib.check(lib.cofi_kpconv_fused(*head, _p(s_pts), *tail, _p(sup), *out), "cofi_kpconv_fused")
     return y, part, sr
 
 
