@@ -139,6 +139,8 @@ SIGNATURES = {
     "cofi_pnp_ransac": (_I, [_P, _P, _P, _I, _F, _F, _F, _F, _I, _F, ctypes.c_uint, _I, _P, _Z, _P, _P, _P, _P]),
     "cofi_pnp_ransac_batch_workspace": (_Z, [_I, _I]),
     "cofi_pnp_ransac_batch": (_I, [_P, _I, _P, _I, _I, _P, _I, _P, _I, _I, _I, _F, ctypes.c_uint, _I, _P, _Z, _P, _P, _P, _P]),
+    "cofi_pnp_ransac_rig_workspace": (_Z, [_I, _I]),
+    "cofi_pnp_ransac_rig": (_I, [_P, _I, _P, _I, _I, _P, _I, _P, _P, _I, _I, _I, _I, _I, _F, ctypes.c_uint, _I, _P, _Z, _P, _P, _P, _P, _P, _P]),
     "cofi_pose_errors": (_I, [_P, _P, _I, _I, _P, _P]),
     "cofi_eval_monitors": (_I, [_P, _I, _P, _I, _I, _P, _I, _P, _I, _I, _P, _P, _P, _I, _P, _I, _P, _P, _I, _P]),
     "cofi_val_gather": (_I, [_P, _I, _I, _I, _I, _P, _I, _I, _P, _P, _I, _I, _I, _P, _P, _P]),

@@ -16,7 +16,13 @@
 //   (cofi_pnp_ransac_batch: frame on the grid, operands addressed through strides, count and intrinsics read on the device; a workgroup
 //   of 4 waves stages its frame's correspondences once in LDS and its 64 hypotheses score from there).  The bodies receive VALUES through
 //   an accessor, so frame f of a batch executes the arithmetic of the per-frame call in the same order: bit-identical results.
+// A third form, the rig (cofi_pnp_ransac_rig): C images of one body, ONE pose.  The bodies take a VIEW that answers how many cameras there
+//   are, how a hypothesis is solved and what each camera scores; a frame of its own is the view with one camera whose compositions are
+//   copies, so the per-frame and batched kernels compute what they always did.  A rig hypothesis is a P3P solve in ONE camera (drawn in
+//   proportion to the cameras' rows) carried into the rig frame through that camera's extrinsics; it is scored and refitted over ALL cameras.
 // Kernel 3 (pose_errors_kernel): RTE / RRE of B poses against ground truth, one thread per frame, fp64.
+#include <type_traits>
+
 #include "common.h"
 #include "pose_errors.h"
 
@@ -198,40 +204,84 @@ struct CorrLds {      // structure of arrays in LDS, `ld` floats apart: x | y | 
     }
 };
 
-// One wave, HPW hypotheses hyp0 .. hyp0 + HPW - 1 (lane h < HPW solves hypothesis hyp0 + h, then all 64 lanes score the HPW poses one
-// after the other).  The body of both hypotheses kernels.
+// The minimal solve of hypothesis `hyp` among n correspondences of one camera: four distinct rows, P3P on three, the fourth picks.
+// pose (fp64, not yet rounded) = that camera <- cloud.
 template <class Corr>
-__device__ __forceinline__ void hypotheses_wave(const Corr &corr, int n, const Cam &cam, int iters, float thr2, unsigned seed, int hyp0,
-                                                float *poses, unsigned long long *best_key) {
+__device__ __forceinline__ bool solve_minimal(const Corr &corr, int n, const Cam &cam, unsigned seed, int hyp, double pose[12]) {
+    int idx[4];
+    for (int j = 0; j < 4; ++j) {
+        int c = (int)(hash_u32(seed, (unsigned)hyp, (unsigned)j) % (unsigned)n);
+        bool again = true;
+        while (again) {
+            again = false;
+            for (int k = 0; k < j; ++k)
+                if (idx[k] == c) { c = (c + 1) % n; again = true; }
+        }
+        idx[j] = c;
+    }
+    double X[3][3], f[3][3];
+    float Xf[3], uvf[2];
+    for (int k = 0; k < 3; ++k) {
+        corr.load(idx[k], Xf, uvf);
+        for (int e = 0; e < 3; ++e) X[k][e] = (double)Xf[e];
+        const double bx = ((double)uvf[0] - cam.cx) / cam.fx, by = ((double)uvf[1] - cam.cy) / cam.fy;
+        const double inv = 1.0 / sqrt(bx * bx + by * by + 1.0);
+        f[k][0] = bx * inv; f[k][1] = by * inv; f[k][2] = inv;
+    }
+    corr.load(idx[3], Xf, uvf);
+    const double X4[3] = {(double)Xf[0], (double)Xf[1], (double)Xf[2]};
+    return p3p_pick(X, f, X4, (double)uvf[0], (double)uvf[1], cam, pose);
+}
+
+// Rig extrinsics, 12 floats per camera [R row-major | t], camera <- rig: Y_cam = R_c Y_rig + t_c.  Everything is composed in fp64 and
+// rounded once by the caller.  With the identity both compositions multiply by 1 and add 0: exact.
+__device__ __forceinline__ void ext_compose(const float *e, const double T[12], double P[12]) {       // P = E o T
+    for (int r = 0; r < 3; ++r) {
+        for (int c = 0; c < 3; ++c) P[3 * r + c] = (double)e[3 * r] * T[c] + (double)e[3 * r + 1] * T[3 + c] + (double)e[3 * r + 2] * T[6 + c];
+        P[9 + r] = (double)e[3 * r] * T[9] + (double)e[3 * r + 1] * T[10] + (double)e[3 * r + 2] * T[11] + (double)e[9 + r];
+    }
+}
+__device__ __forceinline__ void ext_compose_inverse(const float *e, const double P[12], double T[12]) {   // T = E^-1 o P
+    const double d[3] = {P[9] - (double)e[9], P[10] - (double)e[10], P[11] - (double)e[11]};
+    for (int r = 0; r < 3; ++r) {
+        for (int c = 0; c < 3; ++c) T[3 * r + c] = (double)e[r] * P[c] + (double)e[3 + r] * P[3 + c] + (double)e[6 + r] * P[6 + c];
+        T[9 + r] = (double)e[r] * d[0] + (double)e[3 + r] * d[1] + (double)e[6 + r] * d[2];
+    }
+}
+
+// What the hypotheses body works on.  A view answers: how many cameras, the minimal solve of a hypothesis (pose of the BODY: the camera
+// of a single frame, the rig of a rig), and per camera what to score (correspondences, intrinsics, the body pose carried into that camera).
+template <class Corr>
+struct OneCameraView {      // a frame of its own: per-frame and batched kernels
+    Corr corr_;
+    int n;
+    Cam cam_;
+    struct Scored {
+        Corr corr;
+        int n;
+        Cam cam;
+        bool scored;
+        __device__ __forceinline__ void carry(const float T[12], float p[12]) const {
+            for (int k = 0; k < 12; ++k) p[k] = T[k];
+        }
+    };
+    __device__ __forceinline__ int cameras() const { return 1; }
+    __device__ __forceinline__ bool solve(unsigned seed, int hyp, double pose[12]) const { return solve_minimal(corr_, n, cam_, seed, hyp, pose); }
+    __device__ __forceinline__ Scored score_camera(int) const { return Scored{corr_, n, cam_, true}; }
+};
+
+// One wave, HPW hypotheses hyp0 .. hyp0 + HPW - 1 (lane h < HPW solves hypothesis hyp0 + h, then all 64 lanes score the HPW poses one
+// after the other, camera by camera; lane h keeps the inlier count of hypothesis hyp0 + h).  The body of all hypotheses kernels.
+template <class View>
+__device__ __forceinline__ void hypotheses_wave(const View &view, int iters, float thr2, unsigned seed, int hyp0, float *poses,
+                                                unsigned long long *best_key) {
     const int lane = threadIdx.x & 63;
     const int hyp = hyp0 + lane;
     float pose_f[12];
     bool ok = false;
     if (lane < HPW && hyp < iters) {
-        int idx[4];
-        for (int j = 0; j < 4; ++j) {
-            int c = (int)(hash_u32(seed, (unsigned)hyp, (unsigned)j) % (unsigned)n);
-            bool again = true;
-            while (again) {
-                again = false;
-                for (int k = 0; k < j; ++k)
-                    if (idx[k] == c) { c = (c + 1) % n; again = true; }
-            }
-            idx[j] = c;
-        }
-        double X[3][3], f[3][3];
-        float Xf[3], uvf[2];
-        for (int k = 0; k < 3; ++k) {
-            corr.load(idx[k], Xf, uvf);
-            for (int e = 0; e < 3; ++e) X[k][e] = (double)Xf[e];
-            const double bx = ((double)uvf[0] - cam.cx) / cam.fx, by = ((double)uvf[1] - cam.cy) / cam.fy;
-            const double inv = 1.0 / sqrt(bx * bx + by * by + 1.0);
-            f[k][0] = bx * inv; f[k][1] = by * inv; f[k][2] = inv;
-        }
-        corr.load(idx[3], Xf, uvf);
-        const double X4[3] = {(double)Xf[0], (double)Xf[1], (double)Xf[2]};
         double pose[12];
-        ok = p3p_pick(X, f, X4, (double)uvf[0], (double)uvf[1], cam, pose);
+        ok = view.solve(seed, hyp, pose);
         if (ok)
             for (int k = 0; k < 12; ++k) {
                 pose_f[k] = (float)pose[k];
@@ -239,21 +289,31 @@ __device__ __forceinline__ void hypotheses_wave(const Corr &corr, int n, const C
             }
     }
     // score the wave's hypotheses one after the other: lanes stride over the correspondences
-    unsigned long long wave_best = 0ull;
-    for (int h = 0; h < HPW; ++h) {
-        if (!__shfl((int)ok, h, 64)) continue;   // uniform
-        float p[12];
+    int mine = 0;
+    for (int c = 0; c < view.cameras(); ++c) {
+        const auto sc = view.score_camera(c);   // workgroup-uniform (a view that stages rows has its barriers in here)
+        if (!sc.scored) continue;
+        float carried[12];
+        if (ok) sc.carry(pose_f, carried);
+        for (int h = 0; h < HPW; ++h) {
+            if (!__shfl((int)ok, h, 64)) continue;   // uniform
+            float p[12];
 #pragma unroll
-        for (int k = 0; k < 12; ++k) p[k] = __shfl(pose_f[k], h, 64);
-        int cnt = 0;
-        for (int i = lane; i < n; i += 64) {
-            float Xi[3], uvi[2];
-            corr.load(i, Xi, uvi);
-            cnt += inlier(p, Xi, uvi, cam, thr2) ? 1 : 0;
+            for (int k = 0; k < 12; ++k) p[k] = __shfl(carried[k], h, 64);
+            int cnt = 0;
+            for (int i = lane; i < sc.n; i += 64) {
+                float Xi[3], uvi[2];
+                sc.corr.load(i, Xi, uvi);
+                cnt += inlier(p, Xi, uvi, sc.cam, thr2) ? 1 : 0;
+            }
+            for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o, 64);
+            mine += lane == h ? cnt : 0;
         }
-        for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o, 64);
-        const unsigned long long key = ((unsigned long long)(unsigned)cnt << 32) | (unsigned long long)(0xFFFFFFFFu - (unsigned)(hyp0 + h));
-        wave_best = key > wave_best ? key : wave_best;
+    }
+    unsigned long long wave_best = ok ? ((unsigned long long)(unsigned)mine << 32) | (unsigned long long)(0xFFFFFFFFu - (unsigned)hyp) : 0ull;
+    for (int o = HPW / 2; o > 0; o >>= 1) {   // lanes >= HPW hold 0
+        const unsigned long long other = __shfl_xor(wave_best, o, 64);
+        wave_best = other > wave_best ? other : wave_best;
     }
     if (lane == 0 && wave_best) atomicMax(best_key, wave_best);
 }
@@ -263,7 +323,7 @@ __global__ __launch_bounds__(64) void pnp_hypotheses_kernel(const float *obj, co
                                                             unsigned long long *best_key) {
     const int n = count_dev ? min(*count_dev, n_max) : n_max;
     if (n < 4) return;
-    hypotheses_wave(CorrGlobal{obj, img, img + 1, 2}, n, cam, iters, thr2, seed, blockIdx.x * HPW, poses, best_key);
+    hypotheses_wave(OneCameraView<CorrGlobal>{CorrGlobal{obj, img, img + 1, 2}, n, cam}, iters, thr2, seed, blockIdx.x * HPW, poses, best_key);
 }
 
 // ---- the batched form: frame on blockIdx.y, operands addressed through strides, intrinsics and counts read on the device
@@ -283,6 +343,16 @@ struct BatchOperands {
 
 constexpr int BATCH_WAVES = 4;   // waves per workgroup of the batched hypotheses kernel: 64 hypotheses share one staged copy of the frame
 
+// the workgroup's copy of n correspondences in LDS, in CorrLds' layout
+__device__ __forceinline__ void stage_rows(const CorrGlobal &g, int n, int ld, float *s_corr) {
+    for (int i = threadIdx.x; i < n; i += 64 * BATCH_WAVES) {
+        float X[3], uv[2];
+        g.load(i, X, uv);
+        s_corr[i] = X[0]; s_corr[ld + i] = X[1]; s_corr[2 * ld + i] = X[2];
+        s_corr[3 * ld + i] = uv[0]; s_corr[4 * ld + i] = uv[1];
+    }
+}
+
 // LDS = true: the workgroup stages its frame's correspondences once in LDS (5 n_max floats, dynamic) and every hypothesis scores from
 // there; false (frames too large for 64 KiB): from global memory, as the per-frame kernel does.  Same values either way.
 template <bool LDS>
@@ -297,21 +367,108 @@ __global__ __launch_bounds__(64 * BATCH_WAVES) void pnp_hypotheses_batch_kernel(
     const int hyp0 = (blockIdx.x * BATCH_WAVES + (threadIdx.x >> 6)) * HPW;
     float *slab = poses + (size_t)f * iters * 12;
     if (LDS) {
-        for (int i = threadIdx.x; i < n; i += 64 * BATCH_WAVES) {
-            float X[3], uv[2];
-            g.load(i, X, uv);
-            s_corr[i] = X[0]; s_corr[op.n_max + i] = X[1]; s_corr[2 * op.n_max + i] = X[2];
-            s_corr[3 * op.n_max + i] = uv[0]; s_corr[4 * op.n_max + i] = uv[1];
-        }
+        stage_rows(g, n, op.n_max, s_corr);
         __syncthreads();
-        hypotheses_wave(CorrLds{s_corr, op.n_max}, n, cam, iters, thr2, seed + (unsigned)f, hyp0, slab, best_keys + f);
+        hypotheses_wave(OneCameraView<CorrLds>{CorrLds{s_corr, op.n_max}, n, cam}, iters, thr2, seed + (unsigned)f, hyp0, slab, best_keys + f);
     } else {
-        hypotheses_wave(g, n, cam, iters, thr2, seed + (unsigned)f, hyp0, slab, best_keys + f);
+        hypotheses_wave(OneCameraView<CorrGlobal>{g, n, cam}, iters, thr2, seed + (unsigned)f, hyp0, slab, best_keys + f);
     }
+}
+
+// ---- the rig form: rig s on blockIdx.y, its C images are frames s C .. s C + C - 1 of the batched operands; ONE pose per rig.
+struct RigOperands {
+    BatchOperands op;
+    const float *ext;          // rig s, camera c: ext + s * ext_stride + 12 c
+    int ext_stride, cameras;   // ext_stride 0: one set of C shared by all rigs
+    __device__ __forceinline__ const float *E(int s, int c) const { return ext + (size_t)s * ext_stride + 12 * c; }
+    __device__ __forceinline__ bool usable(int f) const { const Cam k = op.cam(f); return k.fx > 0.f && k.fy > 0.f; }
+    // rows of the eligible cameras (usable, at least 4 rows) of rig s, in camera order
+    __device__ __forceinline__ int total(int s) const {
+        int t = 0;
+        for (int c = 0; c < cameras; ++c) {
+            const int f = s * cameras + c, n = op.rows(f);
+            t += (n >= 4 && usable(f)) ? n : 0;
+        }
+        return t;
+    }
+};
+
+// STAGED: camera by camera, the workgroup stages the camera's valid rows in LDS (the footprint of the batched kernel whatever C is), its
+// 64 hypotheses score them, barrier, next camera.  The four sampled rows are read from global memory either way.
+template <bool STAGED>
+struct RigView {
+    RigOperands rig;
+    int s, total;
+    float *s_corr;
+    struct Scored {
+        typename std::conditional<STAGED, CorrLds, CorrGlobal>::type corr;
+        int n;
+        Cam cam;
+        bool scored;
+        const float *e;
+        __device__ __forceinline__ void carry(const float T[12], float p[12]) const {
+            double Td[12], P[12];
+            for (int k = 0; k < 12; ++k) Td[k] = (double)T[k];
+            ext_compose(e, Td, P);
+            for (int k = 0; k < 12; ++k) p[k] = (float)P[k];
+        }
+    };
+    __device__ __forceinline__ int cameras() const { return rig.cameras; }
+    __device__ __forceinline__ bool solve(unsigned seed, int hyp, double pose[12]) const {
+        int g = (int)(hash_u32(seed, (unsigned)hyp, 4u) % (unsigned)total);   // the camera: proportional to its rows
+        int c = 0, n = 0;
+        for (; c < rig.cameras; ++c) {
+            const int f = s * rig.cameras + c;
+            n = rig.op.rows(f);
+            if (n < 4 || !rig.usable(f)) continue;
+            if (g < n) break;
+            g -= n;
+        }
+        const int f = s * rig.cameras + c;
+        double pc[12];
+        if (!solve_minimal(rig.op.corr(f), n, rig.op.cam(f), seed, hyp, pc)) return false;
+        ext_compose_inverse(rig.E(s, c), pc, pose);
+        return true;
+    }
+    __device__ __forceinline__ Scored score_camera(int c) const {
+        const int f = s * rig.cameras + c, n = rig.op.rows(f);
+        const bool scored = n >= 1 && rig.usable(f);
+        const CorrGlobal g = rig.op.corr(f);
+        if constexpr (STAGED) {
+            if (scored) {           // rig-uniform, so every wave of the workgroup arrives
+                __syncthreads();    // the previous camera's rows have been scored
+                stage_rows(g, n, rig.op.n_max, s_corr);
+                __syncthreads();
+            }
+            return Scored{CorrLds{s_corr, rig.op.n_max}, n, rig.op.cam(f), scored, rig.E(s, c)};
+        } else {
+            return Scored{g, n, rig.op.cam(f), scored, rig.E(s, c)};
+        }
+    }
+};
+
+template <bool STAGED>
+__global__ __launch_bounds__(64 * BATCH_WAVES) void pnp_hypotheses_rig_kernel(RigOperands rig, int iters, float thr2, unsigned seed,
+                                                                              float *poses, unsigned long long *best_keys) {
+    extern __shared__ float s_corr[];
+    const int s = blockIdx.y;
+    const int total = rig.total(s);
+    if (total == 0) return;   // rig-uniform: no eligible camera, the key stays 0 and the refit reports failure
+    const int hyp0 = (blockIdx.x * BATCH_WAVES + (threadIdx.x >> 6)) * HPW;
+    hypotheses_wave(RigView<STAGED>{rig, s, total, s_corr}, iters, thr2, seed + (unsigned)s, hyp0, poses + (size_t)s * iters * 12, best_keys + s);
 }
 
 // ---- refit: Levenberg-Marquardt on the inliers of the winning hypothesis
 constexpr int NACC = 28;  // 21 (upper JtJ) + 6 (Jt r) + 1 (cost)
+
+// the normal equations gain one residual pair: rows J0, J1 of its 2x6 Jacobian, residuals r0, r1
+__device__ __forceinline__ void accumulate_rows(const double J0[6], const double J1[6], double r0, double r1, double acc[NACC]) {
+    int k = 0;
+    for (int i = 0; i < 6; ++i)
+        for (int j = i; j < 6; ++j) acc[k++] += J0[i] * J0[j] + J1[i] * J1[j];
+    for (int i = 0; i < 6; ++i) acc[21 + i] += J0[i] * r0 + J1[i] * r1;
+    acc[27] += r0 * r0 + r1 * r1;
+}
 
 __device__ void accumulate(const double R[9], const double t[3], const float *X, const float *uv, const Cam &cam, double acc[NACC]) {
     const double x = R[0] * X[0] + R[1] * X[1] + R[2] * X[2] + t[0], y = R[3] * X[0] + R[4] * X[1] + R[5] * X[2] + t[1],
@@ -323,18 +480,129 @@ __device__ void accumulate(const double R[9], const double t[3], const float *X,
     // -[Y]x = [[0, z, -y], [-z, 0, x], [y, -x, 0]]
     const double J0[6] = {a02 * y, a00 * z - a02 * x, -a00 * y, a00, 0.0, a02};
     const double J1[6] = {-a11 * z + a12 * y, -a12 * x, a11 * x, 0.0, a11, a12};
-    int k = 0;
-    for (int i = 0; i < 6; ++i)
-        for (int j = i; j < 6; ++j) acc[k++] += J0[i] * J0[j] + J1[i] * J1[j];
-    for (int i = 0; i < 6; ++i) acc[21 + i] += J0[i] * r0 + J1[i] * r1;
-    acc[27] += r0 * r0 + r1 * r1;
+    accumulate_rows(J0, J1, r0, r1, acc);
 }
 
-// One workgroup of 256 threads refits one frame.  The body of both refit kernels.
+// a row of camera c of a rig: the pose (R, t) is the RIG's; the point is carried on into the camera, Y_c = R_c (R X + t) + t_c, and the
+// Jacobian with respect to the rig's left-multiplied increment is d(pi)/dY_c . R_c . [-[Y_rig]x | I]
+__device__ void accumulate_rig(const double R[9], const double t[3], const float *e, const float *X, const float *uv, const Cam &cam,
+                               double acc[NACC]) {
+    const double xr = R[0] * X[0] + R[1] * X[1] + R[2] * X[2] + t[0], yr = R[3] * X[0] + R[4] * X[1] + R[5] * X[2] + t[1],
+                 zr = R[6] * X[0] + R[7] * X[1] + R[8] * X[2] + t[2];
+    const double x = (double)e[0] * xr + (double)e[1] * yr + (double)e[2] * zr + (double)e[9],
+                 y = (double)e[3] * xr + (double)e[4] * yr + (double)e[5] * zr + (double)e[10],
+                 z = (double)e[6] * xr + (double)e[7] * yr + (double)e[8] * zr + (double)e[11];
+    const double iz = 1.0 / z;
+    const double r0 = cam.fx * x * iz + cam.cx - uv[0], r1 = cam.fy * y * iz + cam.cy - uv[1];
+    const double a00 = cam.fx * iz, a02 = -cam.fx * x * iz * iz, a11 = cam.fy * iz, a12 = -cam.fy * y * iz * iz;
+    double A0[3], A1[3];   // d(pi)/dY_c . R_c
+    for (int j = 0; j < 3; ++j) {
+        A0[j] = a00 * (double)e[j] + a02 * (double)e[6 + j];
+        A1[j] = a11 * (double)e[3 + j] + a12 * (double)e[6 + j];
+    }
+    const double J0[6] = {A0[2] * yr - A0[1] * zr, A0[0] * zr - A0[2] * xr, A0[1] * xr - A0[0] * yr, A0[0], A0[1], A0[2]};
+    const double J1[6] = {A1[2] * yr - A1[1] * zr, A1[0] * zr - A1[2] * xr, A1[1] * xr - A1[0] * yr, A1[0], A1[1], A1[2]};
+    accumulate_rows(J0, J1, r0, r1, acc);
+}
+
+// What the refit body works on: the cameras of the body whose pose is refitted (one for a frame of its own, C for a rig), and where
+// the outcome goes.
 template <class Corr>
-__device__ __forceinline__ void refine_workgroup(const Corr &corr, int n, int n_max, const Cam &cam, float thr2, const float *poses,
-                                                 const unsigned long long *best_key, int lm_iters, float *pose_out,
-                                                 int32_t *result /* [0] success, [1] inliers, [2] hypothesis */, uint8_t *mask) {
+struct OneFrameView {
+    Corr corr_;
+    int n, n_max;
+    Cam cam_;
+    float *pose_out;
+    int32_t *result;   // [0] success, [1] inliers, [2] hypothesis
+    uint8_t *mask_;
+    struct Camera {
+        Corr corr;
+        int n, n_max;
+        Cam cam;
+        uint8_t *mask;
+        bool scored;
+        __device__ __forceinline__ void carry(const double T[12], float p[12]) const {
+            for (int k = 0; k < 12; ++k) p[k] = (float)T[k];
+        }
+        __device__ __forceinline__ void accumulate_row(const double R[9], const double t[3], const float *X, const float *uv, double acc[NACC]) const {
+            accumulate(R, t, X, uv, cam, acc);
+        }
+        __device__ __forceinline__ void set_inliers(int) const {}
+    };
+    __device__ __forceinline__ int cameras() const { return 1; }
+    __device__ __forceinline__ bool solvable() const { return n >= 4; }
+    __device__ __forceinline__ Camera camera(int) const { return Camera{corr_, n, n_max, cam_, mask_, true}; }
+    __device__ __forceinline__ void fail() const {   // one thread
+        result[0] = 0; result[1] = 0; result[2] = -1;
+        for (int k = 0; k < 12; ++k) pose_out[k] = (k == 0 || k == 4 || k == 8) ? 1.f : 0.f;
+    }
+    __device__ __forceinline__ void succeed(const double pose[12], int inliers, int hyp) const {   // one thread
+        for (int k = 0; k < 12; ++k) pose_out[k] = (float)pose[k];
+        result[0] = 1; result[1] = inliers; result[2] = hyp;
+    }
+};
+
+struct RigRefitView {
+    RigOperands rig;
+    int s;
+    float *rig_pose, *pose;          // of this rig (12), of image 0 of this rig (C x 12)
+    int32_t *rig_result, *result;    // of this rig (3), of image 0 of this rig (C x 3)
+    uint8_t *mask_;                  // of image 0 of this rig (C x n_max)
+    struct Camera {
+        CorrGlobal corr;
+        int n, n_max;
+        Cam cam;
+        uint8_t *mask;
+        bool scored;
+        const float *e;
+        int32_t *result;
+        __device__ __forceinline__ void carry(const double T[12], float p[12]) const {
+            double P[12];
+            ext_compose(e, T, P);
+            for (int k = 0; k < 12; ++k) p[k] = (float)P[k];
+        }
+        __device__ __forceinline__ void accumulate_row(const double R[9], const double t[3], const float *X, const float *uv, double acc[NACC]) const {
+            accumulate_rig(R, t, e, X, uv, cam, acc);
+        }
+        __device__ __forceinline__ void set_inliers(int c) const { result[1] = c; }
+    };
+    __device__ __forceinline__ int cameras() const { return rig.cameras; }
+    __device__ __forceinline__ bool solvable() const { return true; }   // a rig without an eligible camera has key 0
+    __device__ __forceinline__ Camera camera(int c) const {
+        const int f = s * rig.cameras + c, n = rig.op.rows(f);
+        return Camera{rig.op.corr(f), n, rig.op.n_max, rig.op.cam(f), mask_ + (size_t)c * rig.op.n_max, n >= 1 && rig.usable(f), rig.E(s, c),
+                      result + 3 * c};
+    }
+    __device__ __forceinline__ void fail() const {
+        for (int c = -1; c < rig.cameras; ++c) {
+            int32_t *r = c < 0 ? rig_result : result + 3 * c;
+            float *p = c < 0 ? rig_pose : pose + 12 * c;
+            r[0] = 0; r[1] = 0; r[2] = -1;
+            for (int k = 0; k < 12; ++k) p[k] = (k == 0 || k == 4 || k == 8) ? 1.f : 0.f;
+        }
+    }
+    // the rig's pose rounded once; every image's pose is the composition E_c o (that float32 pose), rounded once: an unscored camera
+    // (no rows, unusable intrinsics) still gets its pose, with the 0 inliers the body left in its result
+    __device__ __forceinline__ void succeed(const double T[12], int inliers, int hyp) const {
+        double Tf[12];
+        for (int k = 0; k < 12; ++k) {
+            rig_pose[k] = (float)T[k];
+            Tf[k] = (double)rig_pose[k];
+        }
+        rig_result[0] = 1; rig_result[1] = inliers; rig_result[2] = hyp;
+        for (int c = 0; c < rig.cameras; ++c) {
+            double P[12];
+            ext_compose(rig.E(s, c), Tf, P);
+            for (int k = 0; k < 12; ++k) pose[12 * c + k] = (float)P[k];
+            result[3 * c] = 1; result[3 * c + 2] = hyp;
+        }
+    }
+};
+
+// One workgroup of 256 threads refits one body (a frame, a rig) on the inliers of all its cameras.  The body of all refit kernels.
+template <class View>
+__device__ __forceinline__ void refine_workgroup(const View &view, float thr2, const float *poses, const unsigned long long *best_key,
+                                                 int lm_iters) {
     __shared__ double s_red[4][NACC];
     __shared__ double s_sys[NACC];     // reduced normal equations of the candidate pose
     __shared__ double s_pose[12], s_cand[12];
@@ -343,44 +611,59 @@ __device__ __forceinline__ void refine_workgroup(const Corr &corr, int n, int n_
     const unsigned long long key = *best_key;
     const int cnt_best = (int)(key >> 32);
     const int hyp = (int)(0xFFFFFFFFu - (unsigned)(key & 0xFFFFFFFFull));
-    for (int i = tid; i < n_max; i += 256) mask[i] = 0;
-    if (n < 4 || key == 0ull || cnt_best < 4) {
-        if (tid == 0) {
-            result[0] = 0; result[1] = 0; result[2] = -1;
-            for (int k = 0; k < 12; ++k) pose_out[k] = (k == 0 || k == 4 || k == 8) ? 1.f : 0.f;
-        }
+    for (int c = 0; c < view.cameras(); ++c) {
+        const auto cv = view.camera(c);
+        for (int i = tid; i < cv.n_max; i += 256) cv.mask[i] = 0;
+    }
+    if (!view.solvable() || key == 0ull || cnt_best < 4) {
+        if (tid == 0) view.fail();
         return;
     }
-    float pf[12];
-    for (int k = 0; k < 12; ++k) pf[k] = poses[(size_t)hyp * 12 + k];
-    if (tid < 12) s_pose[tid] = (double)pf[tid];
-    // inlier mask of the RANSAC model (what cv2 returns as `inliers`)
-    int c = 0;
-    for (int i = tid; i < n; i += 256) {
-        float Xi[3], uvi[2];
-        corr.load(i, Xi, uvi);
-        const bool in = inlier(pf, Xi, uvi, cam, thr2);
-        mask[i] = in ? 1 : 0;
-        c += in ? 1 : 0;
+    double pd[12];
+    for (int k = 0; k < 12; ++k) pd[k] = (double)poses[(size_t)hyp * 12 + k];
+    if (tid < 12) s_pose[tid] = pd[tid];
+    // inlier masks of the RANSAC model (what cv2 returns as `inliers`), camera by camera
+    int n_in = 0;
+    for (int cc = 0; cc < view.cameras(); ++cc) {
+        const auto cv = view.camera(cc);
+        int c = 0;
+        if (cv.scored) {
+            float pf[12];
+            cv.carry(pd, pf);
+            for (int i = tid; i < cv.n; i += 256) {
+                float Xi[3], uvi[2];
+                cv.corr.load(i, Xi, uvi);
+                const bool in = inlier(pf, Xi, uvi, cv.cam, thr2);
+                cv.mask[i] = in ? 1 : 0;
+                c += in ? 1 : 0;
+            }
+        }
+        for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
+        if (lane == 0) s_cnt[wv] = c;
+        __syncthreads();
+        const int n_cam = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
+        if (tid == 0) cv.set_inliers(n_cam);
+        n_in += n_cam;
+        if (cc + 1 < view.cameras()) __syncthreads();   // s_cnt is reused
     }
-    for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
-    if (lane == 0) s_cnt[wv] = c;
-    __syncthreads();
-    const int n_in = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
 
-    // normal equations at `pose` over the inliers, reduced in a fixed order: thread-strided partials -> wave butterflies -> 4 waves
+    // normal equations at `pose` over the inliers, reduced in a fixed order: camera-major, thread-strided partials -> wave butterflies -> 4 waves
     auto reduce_at = [&](const double *pose) {
         double acc[NACC];
         for (int k = 0; k < NACC; ++k) acc[k] = 0.0;
         double R[9], t[3];
         for (int k = 0; k < 9; ++k) R[k] = pose[k];
         for (int k = 0; k < 3; ++k) t[k] = pose[9 + k];
-        for (int i = tid; i < n; i += 256)
-            if (mask[i]) {
-                float Xi[3], uvi[2];
-                corr.load(i, Xi, uvi);
-                accumulate(R, t, Xi, uvi, cam, acc);
-            }
+        for (int cc = 0; cc < view.cameras(); ++cc) {
+            const auto cv = view.camera(cc);
+            if (!cv.scored) continue;
+            for (int i = tid; i < cv.n; i += 256)
+                if (cv.mask[i]) {
+                    float Xi[3], uvi[2];
+                    cv.corr.load(i, Xi, uvi);
+                    cv.accumulate_row(R, t, Xi, uvi, acc);
+                }
+        }
         for (int k = 0; k < NACC; ++k) {
             const double v = wave_sum_d(acc[k]);
             if (lane == 0) s_red[wv][k] = v;
@@ -458,17 +741,15 @@ __device__ __forceinline__ void refine_workgroup(const Corr &corr, int n, int n_
         }
         __syncthreads();
     }
-    if (tid == 0) {
-        for (int k = 0; k < 12; ++k) pose_out[k] = (float)s_pose[k];
-        result[0] = 1; result[1] = n_in; result[2] = hyp;
-    }
+    if (tid == 0) view.succeed(s_pose, n_in, hyp);
 }
 
 __global__ __launch_bounds__(256) void pnp_refine_kernel(const float *obj, const float *img, const int32_t *count_dev, int n_max, Cam cam,
                                                          float thr2, const float *poses, const unsigned long long *best_key, int lm_iters,
                                                          float *pose_out, int32_t *result, uint8_t *mask) {
     const int n = count_dev ? min(*count_dev, n_max) : n_max;
-    refine_workgroup(CorrGlobal{obj, img, img + 1, 2}, n, n_max, cam, thr2, poses, best_key, lm_iters, pose_out, result, mask);
+    refine_workgroup(OneFrameView<CorrGlobal>{CorrGlobal{obj, img, img + 1, 2}, n, n_max, cam, pose_out, result, mask}, thr2, poses, best_key,
+                     lm_iters);
 }
 
 // frame f = blockIdx.x: pose_out (frames, 12), result (frames, 3), mask (frames, n_max).  A frame the hypotheses kernel left at once
@@ -477,8 +758,19 @@ __global__ __launch_bounds__(256) void pnp_refine_batch_kernel(BatchOperands op,
                                                                const unsigned long long *best_keys, int lm_iters, float *pose_out,
                                                                int32_t *result, uint8_t *mask) {
     const int f = blockIdx.x;
-    refine_workgroup(op.corr(f), op.rows(f), op.n_max, op.cam(f), thr2, poses + (size_t)f * iters * 12, best_keys + f, lm_iters,
-                     pose_out + 12 * f, result + 3 * f, mask + (size_t)f * op.n_max);
+    refine_workgroup(OneFrameView<CorrGlobal>{op.corr(f), op.rows(f), op.n_max, op.cam(f), pose_out + 12 * f, result + 3 * f,
+                                              mask + (size_t)f * op.n_max},
+                     thr2, poses + (size_t)f * iters * 12, best_keys + f, lm_iters);
+}
+
+// rig s = blockIdx.x: rig_pose (rigs, 12), rig_result (rigs, 3); per image pose (rigs C, 12), result (rigs C, 3), mask (rigs C, n_max)
+__global__ __launch_bounds__(256) void pnp_refine_rig_kernel(RigOperands rig, int iters, float thr2, const float *poses,
+                                                             const unsigned long long *best_keys, int lm_iters, float *rig_pose,
+                                                             int32_t *rig_result, float *pose, int32_t *result, uint8_t *mask) {
+    const int s = blockIdx.x;
+    const size_t f0 = (size_t)s * rig.cameras;
+    refine_workgroup(RigRefitView{rig, s, rig_pose + 12 * s, pose + 12 * f0, rig_result + 3 * s, result + 3 * f0, mask + f0 * rig.op.n_max}, thr2,
+                     poses + (size_t)s * iters * 12, best_keys + s, lm_iters);
 }
 
 // ---- registration errors of B poses (evaluation/eval_all.py:16-22): P_diff = inv(P_pred) P_gt, RTE = |t|, RRE = sum |euler 'xzy'| in degrees
@@ -544,6 +836,38 @@ extern "C" int cofi_pnp_ransac_batch(const float *obj, int obj_frame_stride, con
         hipLaunchKernelGGL(pnp_hypotheses_batch_kernel<false>, grid, block, 0, s, op, iterations, thr2, seed, poses, keys);
     hipLaunchKernelGGL(pnp_refine_batch_kernel, dim3(frames), dim3(256), 0, s, op, iterations, thr2, poses, keys, refine_iters, pose, result,
                        inlier_mask);
+    return cofi_launch_status();
+}
+
+// workspace of the rig call: the batched layout with one key and one slab per RIG (the slab holds rig poses)
+extern "C" size_t cofi_pnp_ransac_rig_workspace(int iterations, int rigs) { return cofi_pnp_ransac_batch_workspace(iterations, rigs); }
+
+extern "C" int cofi_pnp_ransac_rig(const float *obj, int obj_frame_stride, const float *img, int img_frame_stride, int coord_major,
+                                   const int32_t *count_dev, int count_stride, const float *K_dev, const float *ext_dev, int ext_rig_stride,
+                                   int n_max, int cameras, int rigs, int iterations, float reproj_err, unsigned seed, int refine_iters,
+                                   void *ws, size_t ws_bytes, float *rig_pose, int32_t *rig_result, float *pose, int32_t *result,
+                                   uint8_t *inlier_mask, cofi_stream_t stream) {
+    if (!obj || !img || !K_dev || !ext_dev || !rig_pose || !rig_result || !pose || !result || !inlier_mask || n_max <= 0 || cameras <= 0 ||
+        rigs <= 0 || (long long)rigs * cameras > 65535 || iterations <= 0 || !(reproj_err > 0.f) || refine_iters < 0 ||
+        obj_frame_stride < 3 * n_max || img_frame_stride < 2 * n_max || (count_dev && count_stride < 1) ||
+        (ext_rig_stride != 0 && ext_rig_stride < 12 * cameras))
+        return COFI_EINVAL;
+    if (!ws || ws_bytes < cofi_pnp_ransac_rig_workspace(iterations, rigs) || ((uintptr_t)ws & 15)) return COFI_EWORKSPACE;
+    hipStream_t s = cofi_s(stream);
+    unsigned long long *keys = (unsigned long long *)ws;
+    float *poses = (float *)((char *)ws + batch_key_bytes(rigs));
+    if (hipError_t e = hipMemsetAsync(keys, 0, batch_key_bytes(rigs), s); e != hipSuccess) return (int)e;
+    const RigOperands rig{BatchOperands{obj, img, count_dev, K_dev, obj_frame_stride, img_frame_stride, count_stride, coord_major ? 1 : 0, n_max},
+                          ext_dev, ext_rig_stride, cameras};
+    const float thr2 = reproj_err * reproj_err;
+    const dim3 grid(cofi_cdiv(iterations, HPW * BATCH_WAVES), rigs), block(64 * BATCH_WAVES);
+    const size_t lds = (size_t)n_max * 5 * sizeof(float);   // one camera's rows at a time: the batched kernel's footprint for any C
+    if (lds <= 64 * 1024)   // by the capacity alone, never by device-side counts
+        hipLaunchKernelGGL(pnp_hypotheses_rig_kernel<true>, grid, block, lds, s, rig, iterations, thr2, seed, poses, keys);
+    else
+        hipLaunchKernelGGL(pnp_hypotheses_rig_kernel<false>, grid, block, 0, s, rig, iterations, thr2, seed, poses, keys);
+    hipLaunchKernelGGL(pnp_refine_rig_kernel, dim3(rigs), dim3(256), 0, s, rig, iterations, thr2, poses, keys, refine_iters, rig_pose,
+                       rig_result, pose, result, inlier_mask);
     return cofi_launch_status();
 }
 

@@ -492,7 +492,7 @@ class CoFiI2P(nn.Module):
 
     @torch.no_grad()
     def forward_async(self, slot: int, pc_data_dict, img, mode: str = "test", inputs_stable: bool = False, pose_K=None,
-                      pose_iterations: int = 10000, pose_seed: int = 0, eval_into=None, cameras: int = 1):
+                      pose_iterations: int = 10000, pose_seed: int = 0, eval_into=None, cameras: int = 1, rig_extrinsics=None):
         """Enqueue one test-mode forward on the CURRENT stream through the hipGraph of slot `slot` and return
         immediately (no host sync).  `img` (1,3,H,W) = one frame, or (B,3,H,W) with a stack-mode `pc_data_dict`
         (see stack_frames) = B frames through the same launches.  Slots own their static buffers and scratch, so
@@ -523,13 +523,36 @@ class CoFiI2P(nn.Module):
         clouds in stack-mode layout (`stack_frames(S pyramids, B images)` builds exactly this input; preprocess.FrameStack(cameras=C)
         fills it in place), and the point encoder runs once per cloud instead of once per image.  Outputs, handle, pose tail (pose_K
         (B,3,3)) and eval_into are those of a stack-mode submission of B frames.  Refused before anything is enqueued: a C that does not
-        divide B, point-side rows that S does not divide."""
+        divide B, point-side rows that S does not divide.
+
+        rig_extrinsics (needs cameras = C > 1 and pose_K): the C cameras are bolted to one body, and the pose tail becomes ONE solve per
+        rig over the matches of all its cameras (pose.solve_pnp_ransac_rig; rig s uses seed pose_seed + s).  (C,4,4) / (C,3,4) shared by
+        all rigs or (S,C,4,4) / (S,C,3,4), camera <- rig (Y_cam = R_c Y_rig + t_c), a host array (checked, copied into a buffer of the
+        slot) or the pair pose.rig_extrinsics returned (read in place: keep it unmodified until `finish()`).  handle["pose"] keeps its
+        four per-image entries - now E_c o rig pose, this image's inliers of the rig's consensus, its mask - so eval_into and every other
+        reader of per-image poses work unchanged, and the handle gains handle["rig_pose"] = {"result" (S,3) int32 [success, inliers over
+        all cameras, hypothesis], "R" (S,3,3), "t" (S,3)}.  Refused before anything is enqueued: rig_extrinsics without pose_K or with
+        cameras == 1."""
         if mode != "test":
             if cameras != 1:
                 raise ValueError("a rig (cameras = %d > 1) serves mode='test' only, got mode=%r" % (cameras, mode))
             raise ValueError("forward_async serves the test-mode pipeline")
         _lib.load()
         self._check_rig(pc_data_dict, img, cameras)
+        if rig_extrinsics is not None:
+            from . import pose as _pose
+
+            if pose_K is None:
+                raise _lib.CofiError("forward_async(rig_extrinsics=...): the rig pose is a pose tail - pass pose_K")
+            if cameras == 1:
+                raise _lib.CofiError("forward_async(rig_extrinsics=...): a rig has cameras > 1; one camera is served by pose_K alone")
+            if not isinstance(rig_extrinsics, tuple):   # checked (and converted) before anything is enqueued
+                rig_extrinsics = _pose.rig_extrinsics(rig_extrinsics, cameras, "cpu")
+            S = (img.shape[0] if img.dim() == 4 else 1) // cameras
+            ext = rig_extrinsics[0]
+            if not (torch.is_tensor(ext) and tuple(ext.shape) in ((cameras, 12), (S, cameras, 12))):
+                raise _lib.CofiError("forward_async(rig_extrinsics=...): need the extrinsics of C = %d cameras, shared or for each of S = %d rigs"
+                                     % (cameras, S))
         if eval_into is not None:
             from . import evaluation
 
@@ -537,7 +560,8 @@ class CoFiI2P(nn.Module):
                 raise _lib.CofiError("forward_async(eval_into=...): the monitors read the submission's poses - pass pose_K")
             evaluation.check_eval_into(eval_into, img.shape[0] if img.dim() == 4 else 1, img.device)
         with ops.arithmetic(self.arithmetic):
-            return self._forward_async(slot, pc_data_dict, img, mode, inputs_stable, pose_K, pose_iterations, pose_seed, eval_into, cameras)
+            return self._forward_async(slot, pc_data_dict, img, mode, inputs_stable, pose_K, pose_iterations, pose_seed, eval_into, cameras,
+                                       rig_extrinsics)
 
     @staticmethod
     def _check_rig(pc_data_dict, img, cameras):
@@ -557,8 +581,9 @@ class CoFiI2P(nn.Module):
                 raise _lib.CofiError("forward_async: B = %d images with C = %d cameras are S = %d clouds, which does not divide the %d rows of %s"
                                      % (B, cameras, S, t.shape[0], name))
 
-    def _enqueue_pose(self, slot, outs, K, iterations, seed):
-        """the batched pose tail of a submission, on the current stream, into buffers the slot owns"""
+    def _enqueue_pose(self, slot, outs, K, iterations, seed, cameras=1, rig_ext=None):
+        """the batched pose tail of a submission (with rig_ext = (ext, rig stride): the rig solve), on the current stream, into buffers
+        the slot owns -> (handle["pose"], K on the device, handle["rig_pose"] or None)"""
         from . import pose as _pose
 
         if "coarse_pts_all" not in outs[0]:
@@ -582,12 +607,29 @@ class CoFiI2P(nn.Module):
         if not (K.is_cuda and K.device == dev and K.dtype == torch.float32 and K.dim() == 3 and K.is_contiguous()):
             b["K"].copy_(K, non_blocking=True)   # broadcasts a (3,3); a device K of another dtype is converted on the device
             K = b["K"]
+        if rig_ext is not None:
+            S = B // cameras
+            ext, estride = rig_ext
+            r = b.get("rig")
+            if r is None:
+                r = b["rig"] = {"ws": torch.empty(_pose.pnp_rig_workspace(iterations, S), dtype=torch.uint8, device=dev),
+                                "pose": torch.empty((S, 12), dtype=torch.float32, device=dev),
+                                "result": torch.empty((S, 3), dtype=torch.int32, device=dev)}
+            if not (ext.is_cuda and ext.device == dev):   # a host set: into a buffer of the slot, as K
+                buf = r.get("ext")
+                if buf is None or buf.shape != ext.shape:
+                    buf = r["ext"] = torch.empty(tuple(ext.shape), dtype=torch.float32, device=dev)
+                buf.copy_(ext, non_blocking=True)
+                ext = buf
+            rig, per = _pose.solve_pnp_ransac_rig_into(cpts, fxy, K, (ext, estride), cameras, cnt[:, 0], r["ws"], r["pose"], r["result"],
+                                                       b["pose"], b["result"], b["mask"], iterations=iterations, seed=seed, coord_major=True)
+            return per, K, rig
         res, R, t, mask = _pose.solve_pnp_ransac_batch_into(cpts, fxy, K, cnt[:, 0], b["ws"], b["pose"], b["result"], b["mask"],
                                                             iterations=iterations, seed=seed, coord_major=True)
-        return {"result": res, "R": R, "t": t, "inliers": mask}, K
+        return {"result": res, "R": R, "t": t, "inliers": mask}, K, None
 
     def _forward_async(self, slot, pc_data_dict, img, mode, inputs_stable, pose_K=None, pose_iterations=10000, pose_seed=0, eval_into=None,
-                       cameras=1):
+                       cameras=1, rig_ext=None):
         P = self._pack(img.device)
         if inputs_stable:
             for k in ("points", "neighbors", "subsampling", "upsampling"):
@@ -608,7 +650,8 @@ class CoFiI2P(nn.Module):
         if host is None:
             host = hosts[(slot, len(outs))] = torch.empty((len(outs), 2), dtype=torch.int32, pin_memory=True)
         host.copy_(outs[0]["count_all"], non_blocking=True)
-        pose, K_dev = (None, None) if pose_K is None else self._enqueue_pose(slot, outs, pose_K, pose_iterations, pose_seed)
+        pose, K_dev, rig_pose = (None, None, None) if pose_K is None else self._enqueue_pose(slot, outs, pose_K, pose_iterations, pose_seed,
+                                                                                             cameras, rig_ext)
         if eval_into is not None:   # the evaluation monitors of the submission: one launch behind the pose tail
             from . import evaluation
 
@@ -618,6 +661,8 @@ class CoFiI2P(nn.Module):
         handle = {"out": outs, "count_host": host, "done": done}
         if pose is not None:
             handle["pose"] = pose
+        if rig_pose is not None:
+            handle["rig_pose"] = rig_pose
         return handle
 
     @torch.no_grad()

@@ -11,7 +11,11 @@ oracle/pnp_oracle.py and against ground-truth poses of synthetic correspondences
 
 For the B frames of a stack-mode submission: `solve_pnp_ransac_batch` (cofi_pnp_ransac_batch: all frames in two launches, operands and
 intrinsics read on the device in the layout the forward leaves them, frame f bit-identical to the per-frame call with seed + f) and
-`pose_errors` (cofi_pose_errors: get_P_diff of B poses on the device)."""
+`pose_errors` (cofi_pose_errors: get_P_diff of B poses on the device).
+
+For the S rigs of a rig submission whose C cameras are bolted to one body: `solve_pnp_ransac_rig` (cofi_pnp_ransac_rig: ONE pose per
+rig, rig <- cloud, from the matches of all its cameras; extrinsics camera <- rig through `rig_extrinsics`; per-image poses composed from
+it)."""
 from typing import Optional
 
 import numpy as np
@@ -139,6 +143,129 @@ def solve_pnp_ransac_batch(object_points: torch.Tensor, image_points: torch.Tens
     mask = torch.empty((B, cap), dtype=torch.uint8, device=dev)
     return solve_pnp_ransac_batch_into(object_points, image_points, K, count, ws, pose, result, mask, iterations, reproj_error, seed,
                                        refine_iters, coord_major)
+
+
+def rig_extrinsics(E, cameras: int, device):
+    """The extrinsics of a rig of C = `cameras` cameras as the rig solver reads them -> (ext, rig_stride): a contiguous float32 device
+    tensor of 12-float rows [R row-major | t], (C,12) with rig_stride 0 (one set shared by all rigs) or (S,C,12) with rig_stride 12 C (one
+    set per rig).  Convention: camera <- rig, Y_cam = R_c Y_rig + t_c.  E: (C,4,4), (C,3,4), (S,C,4,4) or (S,C,3,4).  A host array /
+    tensor is checked (rotation block orthonormal to within 1e-4, the rounding of a calibration file; bottom row [0,0,0,1]) and
+    uploaded; a device tensor is read as it is, without a download."""
+    Err = _lib.CofiError
+    C = int(cameras)
+    shape = tuple(E.shape) if hasattr(E, "shape") else tuple(np.asarray(E).shape)
+    if C < 1 or len(shape) not in (3, 4) or shape[-1] != 4 or shape[-2] not in (3, 4) or shape[-3] != C or (len(shape) == 4 and shape[0] < 1):
+        raise Err("rig_extrinsics: need (C,4,4), (C,3,4), (S,C,4,4) or (S,C,3,4) with C = %d cameras, got %s" % (C, shape))
+    if torch.is_tensor(E) and E.is_cuda:
+        ext = E[..., :3, :]
+    else:
+        Eh = E.detach().cpu().numpy() if torch.is_tensor(E) else np.asarray(E)
+        Eh = Eh.astype(np.float64)
+        if not np.isfinite(Eh).all():
+            raise Err("rig_extrinsics: non-finite entries")
+        if shape[-2] == 4 and not np.array_equal(Eh[..., 3, :], np.broadcast_to(np.array([0.0, 0.0, 0.0, 1.0]), Eh[..., 3, :].shape)):
+            raise Err("rig_extrinsics: the bottom row of every matrix must be [0, 0, 0, 1]")
+        R = Eh[..., :3, :3]
+        off = np.abs(R @ np.swapaxes(R, -1, -2) - np.eye(3)).max()
+        if off > 1e-4 or (np.linalg.det(R) < 0).any():
+            raise Err("rig_extrinsics: a rotation block is not orthonormal to within 1e-4 (max |R R^T - I| = %.3g) or is a reflection" % off)
+        ext = torch.from_numpy(np.ascontiguousarray(Eh[..., :3, :], dtype=np.float32))
+    # [R | t] rows (3,4) -> R row-major (9) | t (3)
+    ext = torch.cat([ext[..., :3].reshape(shape[:-2] + (9,)), ext[..., 3]], -1).to(device=device, dtype=torch.float32).contiguous()
+    return ext, (12 * C if ext.dim() == 3 else 0)
+
+
+def pnp_rig_workspace(iterations: int, rigs: int) -> int:
+    return _lib.load().cofi_pnp_ransac_rig_workspace(int(iterations), int(rigs))
+
+
+def pnp_rig_workspace_views(ws: torch.Tensor, iterations: int, rigs: int):
+    """(keys, poses): views of a workspace of solve_pnp_ransac_rig_into, as pnp_batch_workspace_views with one key and one slab per RIG:
+    keys (rigs,) int64, poses (rigs, iterations, 12) float32 - row h of a rig is hypothesis h as a RIG pose (rig <- cloud), written only
+    if that hypothesis produced a pose.  For tests and tools."""
+    iterations, rigs = int(iterations), int(rigs)
+    need = pnp_rig_workspace(iterations, rigs)
+    slab_bytes = rigs * iterations * 12 * 4
+    if not (torch.is_tensor(ws) and ws.dtype == torch.uint8 and ws.dim() == 1 and ws.is_contiguous() and need > 0 and ws.numel() >= need):
+        raise _lib.CofiError("pnp_rig_workspace_views: ws must be a contiguous uint8 tensor of at least pnp_rig_workspace(%d, %d) = %d bytes"
+                             % (iterations, rigs, need))
+    key_bytes = need - slab_bytes
+    return ws[:8 * rigs].view(torch.int64), ws[key_bytes:need].view(torch.float32).view(rigs, iterations, 12)
+
+
+def _rig_operands(object_points, image_points, K, extrinsics, cameras, count, coord_major, what):
+    """checks of the rig call -> (B, cap, S, K, count, count stride, ext, ext rig stride)"""
+    B, cap, K, count, cstride = _batch_operands(object_points, image_points, K, count, coord_major, what)
+    if not isinstance(cameras, int) or cameras < 1:
+        raise _lib.CofiError("%s: cameras must be an integer >= 1, got %r" % (what, cameras))
+    if B % cameras:
+        raise _lib.CofiError("%s: B = %d images are no whole number of rigs of C = %d cameras" % (what, B, cameras))
+    S = B // cameras
+    if isinstance(extrinsics, tuple):   # (ext, rig_stride) of rig_extrinsics
+        ext, estride = extrinsics
+        if not (torch.is_tensor(ext) and ext.is_cuda and ext.device == object_points.device and ext.dtype == torch.float32 and ext.is_contiguous()
+                and tuple(ext.shape) in ((cameras, 12), (S, cameras, 12)) and estride == (12 * cameras if ext.dim() == 3 else 0)):
+            raise _lib.CofiError("%s: extrinsics given as (ext, rig_stride) must be what rig_extrinsics returns for C = %d cameras%s"
+                                 % (what, cameras, " and S = %d rigs" % S))
+    else:
+        ext, estride = rig_extrinsics(extrinsics, cameras, object_points.device)
+        if ext.dim() == 3 and ext.shape[0] != S:
+            raise _lib.CofiError("%s: per-rig extrinsics for %d rigs, but B / C = %d" % (what, ext.shape[0], S))
+    return B, cap, S, K, count, cstride, ext, estride
+
+
+def solve_pnp_ransac_rig_into(object_points, image_points, K, extrinsics, cameras, count, ws, rig_pose, rig_result, pose, result, mask,
+                              iterations: int = 10000, reproj_error: float = 8.0, seed: int = 0, refine_iters: int = 20,
+                              coord_major: bool = False):
+    """solve_pnp_ransac_rig into caller-owned buffers (ws uint8, rig_pose (S,12) float32, rig_result (S,3) int32, pose (B,12) float32,
+    result (B,3) int32, mask (B,cap) uint8).  extrinsics: what solve_pnp_ransac_rig takes, or the pair rig_extrinsics returned (nothing
+    is converted then).  Enqueues a memset and two kernels on the current stream; nothing else."""
+    lib = _lib.load()
+    what = "solve_pnp_ransac_rig"
+    B, cap, S, K, count, cstride, ext, estride = _rig_operands(object_points, image_points, K, extrinsics, cameras, count, coord_major, what)
+    for t_, shape, dt in ((rig_pose, (S, 12), torch.float32), (rig_result, (S, 3), torch.int32), (pose, (B, 12), torch.float32),
+                          (result, (B, 3), torch.int32), (mask, (B, cap), torch.uint8)):
+        if not (torch.is_tensor(t_) and t_.is_cuda and t_.dtype == dt and tuple(t_.shape) == shape and t_.is_contiguous()):
+            raise _lib.CofiError("%s: output buffers must be contiguous CUDA tensors rig_pose (S,12) float32, rig_result (S,3) int32, pose (B,12) "
+                                 "float32, result (B,3) int32, mask (B,cap) uint8" % what)
+    if not (torch.is_tensor(ws) and ws.is_cuda and ws.dtype == torch.uint8 and ws.is_contiguous()):
+        raise _lib.CofiError("%s: ws must be a contiguous CUDA uint8 tensor" % what)
+    rc = lib.cofi_pnp_ransac_rig(ops._p(object_points), 3 * cap, ops._p(image_points), 2 * cap, 1 if coord_major else 0, ops._p(count), cstride,
+                                 ops._p(K), ops._p(ext), int(estride), cap, int(cameras), S, int(iterations), float(reproj_error),
+                                 int(seed) & 0xFFFFFFFF, int(refine_iters), ops._p(ws), ws.numel(), ops._p(rig_pose), ops._p(rig_result),
+                                 ops._p(pose), ops._p(result), ops._p(mask), ops._stream())
+    _lib.check(rc, "cofi_pnp_ransac_rig")
+    return ({"result": rig_result, "R": rig_pose[:, :9].view(S, 3, 3), "t": rig_pose[:, 9:]},
+            {"result": result, "R": pose[:, :9].view(B, 3, 3), "t": pose[:, 9:], "inliers": mask})
+
+
+def solve_pnp_ransac_rig(object_points: torch.Tensor, image_points: torch.Tensor, K, extrinsics, cameras: int,
+                         count: Optional[torch.Tensor] = None, iterations: int = 10000, reproj_error: float = 8.0, seed: int = 0,
+                         refine_iters: int = 20, coord_major: bool = False):
+    """ONE pose per rig from the matches of all its cameras (cofi_pnp_ransac_rig).  The operands are those of solve_pnp_ransac_batch for
+    B = S * C images, image f = s * C + c being camera c of rig s (the layout of forward_async(..., cameras=C)); extrinsics: (C,4,4) /
+    (C,3,4) shared by all rigs or (S,C,4,4) / (S,C,3,4), camera <- rig (Y_cam = R_c Y_rig + t_c), host array or device tensor (see
+    rig_extrinsics).  Every hypothesis is a P3P solve in one camera - drawn in proportion to the cameras' rows among those with usable
+    intrinsics and at least 4 rows - carried into the rig frame and scored over every camera; the winner is refitted on all cameras'
+    inliers.  Cameras with fewer than 4 matches therefore contribute, but a rig whose cameras ALL have fewer than 4 fails even if the rows
+    add up to more: there is no minimal solver across cameras (generalised P3P) here.  Rig s uses seed + s; at C = 1 with identity
+    extrinsics the call is solve_pnp_ransac_batch.
+
+    Returns (rig, per_image): rig = {"result" (S,3) int32 [success, inliers over all cameras, hypothesis], "R" (S,3,3), "t" (S,3)} is the
+    pose rig <- cloud; per_image = {"result" (B,3) [rig success, this image's inliers, hypothesis], "R" (B,3,3), "t" (B,3), "inliers"
+    (B,cap) uint8} holds E_c o rig pose, so whatever reads per-image poses keeps working.  A failed rig: [0,0,-1], identity poses, zero
+    masks.  Device tensors, no host synchronisation: the call can be captured in a hipGraph."""
+    B, cap, S, K, count, _, ext, estride = _rig_operands(object_points, image_points, K, extrinsics, cameras, count, coord_major,
+                                                         "solve_pnp_ransac_rig")
+    dev = object_points.device
+    ws = torch.empty(pnp_rig_workspace(iterations, S), dtype=torch.uint8, device=dev)
+    rig_pose = torch.empty((S, 12), dtype=torch.float32, device=dev)
+    rig_result = torch.empty((S, 3), dtype=torch.int32, device=dev)
+    pose = torch.empty((B, 12), dtype=torch.float32, device=dev)
+    result = torch.empty((B, 3), dtype=torch.int32, device=dev)
+    mask = torch.empty((B, cap), dtype=torch.uint8, device=dev)
+    return solve_pnp_ransac_rig_into(object_points, image_points, K, (ext, estride), cameras, count, ws, rig_pose, rig_result, pose, result,
+                                     mask, iterations, reproj_error, seed, refine_iters, coord_major)
 
 
 def pose_errors(pose, P_gt) -> torch.Tensor:

@@ -30,6 +30,12 @@ Rigs (one cloud under C images: the cameras around one sweep, a stereo pair): `F
 of C, and `submit_rig(pyr, imgs (C,3,H,W), K (C,3,3), P_gt (C,4,4), rows)` -> C tickets, one per image, used like the tickets of `submit`.
 A stack then holds B // C clouds and B images and is submitted with `forward_async(..., cameras=C)`: the point encoder runs once per
 cloud.  A partly filled stack is completed with copies of its last RIG.
+
+Rig pose (the C cameras are bolted to one body: ONE pose per rig from the matches of all its cameras, `pose.solve_pnp_ransac_rig`):
+`FrameBatcher(model, batch=B, cameras=C, pose=True, rig_extrinsics=E)` with E (C,4,4) / (C,3,4), camera <- rig (Y_cam = R_c Y_rig + t_c),
+for every rig, or `rig_extrinsics="per_rig"` and `submit_rig(..., extrinsics=E)` with each rig's own (C,4,4) / (C,3,4).
+`rig_pose_result(t)` -> (result (3,) int32 [success, inliers over all cameras, hypothesis], R (3,3), t (3,)) of the ticket's rig, rig <-
+cloud; `pose_result(t)` stays per image and holds E_c o rig pose with that image's share of the consensus.
 """
 from typing import Dict, List, Optional, Tuple
 
@@ -41,7 +47,7 @@ from .preprocess import FrameStack
 
 class FrameBatcher:
     def __init__(self, model: CoFiI2P, batch: int = 16, streams: int = 4, ring: Optional[int] = None, slot_base: int = 200,
-                 pose: bool = False, pose_iterations: int = 10000, eval_table=None, cameras: int = 1):
+                 pose: bool = False, pose_iterations: int = 10000, eval_table=None, cameras: int = 1, rig_extrinsics=None):
         if batch < 1:
             raise ValueError("batch must be >= 1")
         if cameras < 1 or batch % cameras:
@@ -70,6 +76,23 @@ class FrameBatcher:
         self.eval_table = eval_table
         self._P: List[Optional[torch.Tensor]] = [None] * self.ring   # (B,4,4) float64 device buffer of each stack: the frames' ground-truth poses
         self._row: List[Optional[torch.Tensor]] = [None] * self.ring  # (B,) int32: the table row of each frame, -1 for padding
+        # rig pose: one set of extrinsics for every rig (converted on first use, when the device is known), or a (S,C,12) buffer per stack
+        self.rig = rig_extrinsics is not None
+        self.rig_per_rig = isinstance(rig_extrinsics, str)
+        if self.rig:
+            if not self.pose or self.C == 1:
+                raise ValueError("FrameBatcher(rig_extrinsics=...): the rig pose needs pose=True and cameras > 1")
+            if self.rig_per_rig and rig_extrinsics != "per_rig":
+                raise ValueError("FrameBatcher(rig_extrinsics=...): extrinsics (C,4,4) / (C,3,4), or 'per_rig' with submit_rig(extrinsics=...)")
+            if not self.rig_per_rig:
+                from . import pose as _pose
+
+                rig_extrinsics = _pose.rig_extrinsics(rig_extrinsics, self.C, "cpu")   # checked here; uploaded once in _rig_ext
+                if rig_extrinsics[0].dim() != 2:
+                    raise ValueError("FrameBatcher(rig_extrinsics=...): one set of (C,4,4) / (C,3,4); per-rig sets go through 'per_rig'")
+        self._ext_shared = None if self.rig_per_rig else rig_extrinsics
+        self._ext: List[Optional[torch.Tensor]] = [None] * self.ring  # (S,C,12) device buffer of each stack (per-rig extrinsics)
+        self._rig_poses: List[Optional[Dict]] = [None] * self.ring    # handle["rig_pose"] of the stack's finished submission
 
     # ------------------------------------------------------------------ internals
     def _stream(self, j: int) -> torch.cuda.Stream:
@@ -88,6 +111,7 @@ class FrameBatcher:
             res = self.model.finish(h, per_frame_errors=True)
             self._results[j] = res if isinstance(res, list) else [res]
             self._poses[j] = h.get("pose")
+            self._rig_poses[j] = h.get("rig_pose")
             self._fine[j] = h["fine_xy"]
             self._counts[j] = [max(0, int(n)) for n in h["count_host"][:, 0]]
         finally:
@@ -96,6 +120,8 @@ class FrameBatcher:
     def _launch(self, j: int):
         st = self._stacks[j]
         rig = {} if self.C == 1 else {"cameras": self.C}
+        if self.rig:
+            rig["rig_extrinsics"] = self._rig_ext(j)
         with torch.cuda.stream(self._stream(j)):
             if self.eval_table is not None:
                 self._handles[j] = self.model.forward_async(self.slot_base + j, st.pyr, st.img, inputs_stable=True, pose_K=self._K[j],
@@ -106,7 +132,7 @@ class FrameBatcher:
                                                             pose_iterations=self.pose_iterations, **rig)
             else:
                 self._handles[j] = self.model.forward_async(self.slot_base + j, st.pyr, st.img, inputs_stable=True, **rig)
-        self._results[j] = self._poses[j] = self._fine[j] = self._counts[j] = None
+        self._results[j] = self._poses[j] = self._fine[j] = self._counts[j] = self._rig_poses[j] = None
         self._nsub += 1
 
     # ------------------------------------------------------------------ API
@@ -119,6 +145,27 @@ class FrameBatcher:
         if tuple(K.shape) != (3, 3):
             raise ValueError("FrameBatcher.submit: K must be a (3,3) camera matrix")
         self._K[j][f].copy_(K, non_blocking=True)
+
+    def _rig_ext(self, j: int):
+        """the (ext, rig stride) pair the stack's submission reads in place"""
+        dev = self._stacks[j].img.device
+        if self.rig_per_rig:
+            return self._ext[j], 12 * self.C
+        if not self._ext_shared[0].is_cuda:
+            self._ext_shared = (self._ext_shared[0].to(dev), 0)
+        return self._ext_shared
+
+    def _put_ext(self, j: int, s: int, E):
+        """the rig's extrinsics -> entry s of the stack's (S,C,12) device buffer (on the submission's stream), as _put_K fills K"""
+        from . import pose as _pose
+
+        dev = self._stacks[j].img.device
+        if self._ext[j] is None:
+            self._ext[j] = torch.zeros((self.B // self.C, self.C, 12), dtype=torch.float32, device=dev)
+        ext, _ = _pose.rig_extrinsics(E, self.C, dev)
+        if ext.dim() != 2:
+            raise ValueError("FrameBatcher.submit_rig: extrinsics must be the rig's (C,4,4) / (C,3,4)")
+        self._ext[j][s].copy_(ext, non_blocking=True)
 
     def _put_eval(self, j: int, f: int, P_gt, row: int):
         """the frame's ground-truth pose and table row -> entry f of the stack's buffers (on the submission's stream); a stack that starts
@@ -177,10 +224,11 @@ class FrameBatcher:
             self._cur, self._fill = (j + 1) % self.ring, 0
         return ticket
 
-    def submit_rig(self, pc_data_dict: Dict, imgs: torch.Tensor, K=None, P_gt=None, rows=None) -> List[Tuple[int, int, int]]:
+    def submit_rig(self, pc_data_dict: Dict, imgs: torch.Tensor, K=None, P_gt=None, rows=None, extrinsics=None) -> List[Tuple[int, int, int]]:
         """one cloud and the C = cameras images that look at it -> C tickets, one per image (for `result`, `fine_xy`, `pose_result`).
         imgs (C,3,H,W); K (C,3,3) camera matrices with pose=True; P_gt (C,4,4) ground-truth poses and rows (C table rows >= 0) with
-        eval_table.  The tensors are read as those of `submit` are."""
+        eval_table; extrinsics (C,4,4) / (C,3,4), camera <- rig, with rig_extrinsics="per_rig".  The tensors are read as those of `submit`
+        are."""
         C = self.C
         if not torch.is_tensor(imgs) or imgs.dim() != 4 or imgs.shape[0] != C:
             raise ValueError("FrameBatcher(cameras=%d): submit_rig() needs the rig's images as one (%d,3,H,W) tensor, got %s"
@@ -189,6 +237,8 @@ class FrameBatcher:
             raise ValueError("FrameBatcher(pose=True): submit_rig() needs the images' camera matrices K (%d,3,3)" % C)
         if self.eval_table is not None and (P_gt is None or rows is None or len(P_gt) != C or len(rows) != C or min(int(r) for r in rows) < 0):
             raise ValueError("FrameBatcher(eval_table=...): submit_rig() needs the images' ground-truth poses P_gt (%d,4,4) and %d table rows >= 0" % (C, C))
+        if self.rig_per_rig != (extrinsics is not None):
+            raise ValueError("FrameBatcher.submit_rig: extrinsics go with rig_extrinsics='per_rig', and only with it")
         j = self._cur
         if self._fill == 0:
             self._collect(j)
@@ -205,6 +255,8 @@ class FrameBatcher:
                 self._stacks[j] = FrameStack(pyr, feats, imgs[0], self.B, cameras=C)
             self._stacks[j].put_cloud(self._fill // C, pyr, feats)
             self._stacks[j].put_image(self._fill, imgs)
+            if self.rig_per_rig:
+                self._put_ext(j, self._fill // C, extrinsics)
             for c in range(C):
                 f = self._fill + c
                 if self.pose:
@@ -232,6 +284,8 @@ class FrameBatcher:
                     self._stacks[j].put_image(f0, img)
                     if self.pose:
                         self._K[j][f0:f0 + self.C].copy_(self._K[j][self._fill - self.C:self._fill])
+                    if self.rig_per_rig:
+                        self._ext[j][f0 // self.C].copy_(self._ext[j][self._fill // self.C - 1])
             else:
                 for f in range(self._fill, self.B):
                     self._stacks[j].put(f, pyr, feats, img)
@@ -288,6 +342,16 @@ class FrameBatcher:
             raise RuntimeError("FrameBatcher: no submission is pending for this ticket")
         p = self._poses[j]
         return p["result"][f], p["R"][f], p["t"][f], p["inliers"][f, :self._counts[j][f]]
+
+    def rig_pose_result(self, ticket: Tuple[int, int, int]):
+        """-> (result (3,) int32 [success, inliers over all cameras, winning hypothesis], R (3,3), t (3,)) of the ticket's RIG (rig <- cloud):
+        the same for the C tickets of a rig.  Device views of the slot's buffers, same lifetime as `result(ticket)`."""
+        if not self.rig:
+            raise RuntimeError("FrameBatcher: built without rig_extrinsics")
+        self.pose_result(ticket)   # the ticket checks, the flush and the collection
+        r = self._rig_poses[ticket[0]]
+        s = ticket[2] // self.C
+        return r["result"][s], r["R"][s], r["t"][s]
 
     @property
     def submissions(self) -> int:

@@ -649,6 +649,28 @@ int cofi_pnp_ransac_batch(const float *obj, int obj_frame_stride, const float *i
                           const int32_t *count_dev, int count_stride, const float *K_dev, int n_max, int frames, int iterations,
                           float reproj_err, unsigned seed, int refine_iters, void *ws, size_t ws_bytes, float *pose, int32_t *result,
                           uint8_t *inlier_mask, cofi_stream_t stream);
+/* ONE pose per rig: the `cameras` = C images of a rig are bolted to one body, and the solver finds the pose of that body (rig <- cloud)
+ * from the matches of all its cameras.  The operands are those of cofi_pnp_ransac_batch for rigs * C frames, image f = s * C + c being
+ * camera c of rig s (the layout of a rig submission), plus
+ *   ext_dev  extrinsics in DEVICE memory, 12 floats per camera [R row-major | t], camera <- rig: Y_cam = R_c Y_rig + t_c; camera c of
+ *            rig s at ext_dev + s * ext_rig_stride + 12 c.  ext_rig_stride 0: one set of C shared by all rigs; >= 12 C: one per rig.
+ * Rig s uses seed + s.  A camera is usable if fx > 0 and fy > 0, eligible if usable with >= 4 rows.  Hypothesis h draws an eligible
+ * camera in proportion to its rows (hash j = 4), four rows of it as the batched solver does (at C = 1: the same samples), solves P3P
+ * there and carries the pose into the rig frame, T = E_c^-1 o pose_c (fp64, rounded once into the slab).  It is scored over every
+ * usable camera with >= 1 row through E_c o T (fp64, rounded once) and the batched solver's inlier test; most inliers in total win,
+ * lowest id on ties.  One workgroup per rig refits T on all cameras' inliers (LM, left-multiplied increments on T).  A rig without an
+ * eligible camera fails even if its rows add up to 4 or more: no minimal solver across cameras (generalised P3P) is included.
+ * Outputs: rig_pose (rigs, 12), rig_result (rigs, 3) = {success, inliers of all cameras, hypothesis}; per image pose (rigs C, 12) =
+ * E_c o rig_pose (fp64, rounded once), result (rigs C, 3) = {rig success, this image's inliers, hypothesis}, inlier_mask (rigs C, n_max).
+ * A failed rig: {0, 0, -1} and identity poses for the rig and all its images, zero masks.  Workspace: one key and one slab of
+ * iterations x 12 floats per RIG (the slab holds rig poses).  The hypotheses kernel stages ONE camera's rows at a time in LDS when
+ * n_max <= 3276 (the batched kernel's footprint whatever C is) and reads global memory beyond: chosen by n_max alone.  A memset and
+ * two launches on `stream`, no host synchronisation.  rigs * cameras <= 65535. */
+size_t cofi_pnp_ransac_rig_workspace(int iterations, int rigs);
+int cofi_pnp_ransac_rig(const float *obj, int obj_frame_stride, const float *img, int img_frame_stride, int coord_major,
+                        const int32_t *count_dev, int count_stride, const float *K_dev, const float *ext_dev, int ext_rig_stride, int n_max,
+                        int cameras, int rigs, int iterations, float reproj_err, unsigned seed, int refine_iters, void *ws, size_t ws_bytes,
+                        float *rig_pose, int32_t *rig_result, float *pose, int32_t *result, uint8_t *inlier_mask, cofi_stream_t stream);
 /* The registration errors of evaluation/eval_all.py:16-22 for `frames` poses: P_diff = inv(P_pred) P_gt (general fp64 inverse),
  * out (frames, 2) float64 = [RTE = |t(P_diff)|, RRE = sum |euler 'xzy' of R(P_diff)| in degrees, scipy's gimbal convention].
  * pose (frames, 12) as cofi_pnp_ransac writes it; P_gt (frames, 4, 4) row-major, float64 if gt_is_f64 != 0, else float32. */
