@@ -61,6 +61,10 @@ SIGNATURES = {
     "cofi_kpconv_aggregate": (_I, [_P, _I, _I, _I, _P, _P, _P, _I, _I, _P, _F, _P, _P, _I, _I, _P, _I, _P, _P]),
     "cofi_kp_pack_support": (_I, [_P, _I, _I, _I, _P, _P, _P]),
     "cofi_kpconv_aggregate_rec": (_I, [_P, _I, _I, _I, _P, _P, _P, _I, _I, _P, _F, _P, _I, _I, _P, _I, _P, _P]),
+    "cofi_kp_bits_words": (_I, [_I]),
+    "cofi_kp_pack_bits": (_I, [_P, _I, _I, _I, _P, _P]),
+    "cofi_kpconv_aggregate_rec_sorted": (_I, [_P, _I, _I, _I, _P, _P, _P, _P, _I, _I, _P, _F, _P, _I, _I, _P, _I, _P, _P]),
+    "cofi_kpconv_aggregate_c4_sorted": (_I, [_P, _P, _I, _I, _P, _P, _I, _I, _P, _F, _P, _I, _P, _I, _P, _P]),
     "cofi_neighbor_maxpool": (_I, [_P, _I, _I, _I, _P, _I, _I, _P, _I, _I, _P, _P]),
     "cofi_gather_rows": (_I, [_P, _I, _I, _I, _P, _I, _I, _P, _I, _I, _P]),
     "cofi_gemm_f16x3_eligible": (_I, [_I, _I, _I, _I, _I]),
@@ -154,6 +158,7 @@ SIGNATURES = {
     "cofi_kpconv_fused_slab_rows": (_I, [_I, _I, _I]),
     "cofi_kpconv_fused": (_I, [_P, _I, _I, _I, _P, _P, _P, _I, _I, _P, _F, _P, _P, _I, _P, _P, _I, _P, _I, _I, _P, _P]),
     "cofi_kpconv_fused_rec": (_I, [_P, _I, _I, _I, _P, _P, _P, _I, _I, _P, _F, _P, _I, _P, _P, _I, _P, _I, _I, _P, _P]),
+    "cofi_kpconv_fused_rec_sorted": (_I, [_P, _I, _I, _I, _P, _P, _P, _P, _I, _I, _P, _F, _P, _I, _P, _P, _I, _P, _I, _I, _P, _P]),
     "cofi_color_jitter_chw": (_I, [_P, _I, _I, _P, _F, _F, _F, _F, _P, _Z, _P]),
     "cofi_pack_transform_scan": (_I, [_P, _I, _P, _P, _P]),
     "cofi_voxel_downsample_workspace": (_Z, [_I]),

@@ -51,7 +51,64 @@ struct KpArgs {
                                    // neighbouring queries whose neighbour rows overlap, so the gather is served from L1 instead of L2.
     const float4 *recs;            // REC kernels: one 16-byte record (x, y, z, flag) per support row in place of s_pts / row_pos, flag = 1.0f
                                    // where the row's feature sum is > 0 (what row_pos holds)
+    // SORTED kernels (they stage from records, so row_pos is free): row_pos carries the flags as a BIT table, kp_bits() - this struct
+    // keeps its layout, and with it every unsorted kernel the instruction stream it had (a longer kernarg block reschedules them)
 };
+
+// ---- SORTED forms: record gathers for the sorted prefix of a neighbour row only ---------------------------------------------------
+// PROMISE of the caller (pyramid key "sorted_tables"): in every row of idx the entries inside [0, N) come first, in
+// ascending order of the canonical fp32 distance of knn_common.h (canon_dist); entries outside [0, N) stand only behind them.
+// The support test d2 < rsup2 is monotone in the distance, so the survivors stand at the front of the row, and the staging - one gather of a
+// 16-byte record per neighbour, 64 lanes on 64 cache lines - is needed for that prefix only.  What the other neighbours contribute is
+// their positive-sum flag (npos counts over ALL H neighbours); it comes from the bit table, 2.5 KB per 20 480-row frame, which stays in
+// the vector L1.  The records are gathered in chunks - neighbours 0 - 15, then 16 - 63, then 64 - 127 - and the wave stops after a chunk
+// as soon as nothing behind it can pass the support test.  Everything else (differences, support test, compaction, steps) is the
+// unsorted form's, on the same records in the same order: identical bits on every table that keeps the promise.
+//
+// STOP RULE.  u = 2^-24.  For a neighbour s of query q let D = |s - q|^2 (exact), c = canon_dist (what the row is sorted by) and
+// d2 = (dx dx + dy dy) + dz dz as this file computes it (what the support test reads).
+//   (a) c = ((-2 dot) + qq) + ss: dot, qq, ss are three-term sums (<= 3u relative to |q||s|, |q|^2, |s|^2, fused or not), the two
+//       additions round once each (u (2|q||s| + |q|^2) and u (|q| + |s|)^2):  |c - D| <= u (4|q|^2 + 4|s|^2 + 10|q||s|) (1 + O(u))
+//       <= 5u (|q| + |s|)^2 =: E(s).  canon_dist's clamp at 1e-12 moves c by at most 1e-12.
+//   (b) d2 = D (1 + e), |e| <= 6u < 2^-21 (one rounding per difference, relative; three products, two sums).
+// Let L be the last neighbour of a chunk, valid, and X any valid neighbour behind it that passes the test: d2_X < rsup2, so
+// D_X < rsup2 (1 + 2^-21) and |s_X| <= |q| + 1.01 rsup.  The row is sorted: c_X >= c_L, hence
+//   D_L <= D_X + E(X) + E(L) + 1e-12,   E(X) <= 5u (2|q| + 1.01 rsup)^2,   E(L) <= 5u (2|q| + sqrt(D_L))^2,
+// and with S = 2|q| + 2 sqrt(d2_L) + rsup (>= both brackets / 1.01):  d2_L (1 - 2^-21) <= D_L < rsup2 (1 + 2^-21) + 10.3u S^2 + 1e-12.
+// The kernel stops after L only if   d2_L >= rsup2 (1 + 2^-10) + 2^-20 S^2   (kp_prefix_done): 16u S^2 against the 10.3u S^2 that can
+// occur, and 2^-10 rsup2 against 2^-20 rsup2 + 1e-12 (rsup > 1e-4) and the roundings of evaluating the rule itself in fp32.  So no
+// such X exists.  The rule reads q, rsup and L only; far from the origin it merely costs another chunk.  The other way to stop is that
+// the chunk's last entry is not a valid index: by the promise nothing valid stands behind it.
+// tests/kpconv_prefix_ref.py emulates (a), (b) and the rule in numpy float32; tests/test_kpconv_prefix_cpu.py holds it to zero misses.
+struct KpStop {
+    float qn2, rsup, rsup2;   // 2 |q|, the support radius and its square
+};
+
+__device__ __forceinline__ bool kp_prefix_done(const float d2_last, const KpStop &k) {
+    const float s = k.qn2 + 2.0f * __builtin_amdgcn_sqrtf(d2_last) + k.rsup;
+    return d2_last >= k.rsup2 * (1.0f + 0x1p-10f) + 0x1p-20f * (s * s);
+}
+
+// a wave-uniform value into a scalar register (it then costs no vector register across the step loop)
+__device__ __forceinline__ float kp_scalar(const float v) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v))); }
+
+// SORTED: the flag bits of the frame of query m: one bit per support row (bit n & 31 of word n >> 5), (N + 31) / 32 words per frame
+__device__ __forceinline__ const uint32_t *kp_bits(const KpArgs &a, const int m) {
+    return reinterpret_cast<const uint32_t *>(a.row_pos) + (size_t)(m / a.Mpf) * ((a.N + 31) >> 5);
+}
+
+// value of lane `src` (compile-time) in a scalar register
+__device__ __forceinline__ float kp_lane_value(const float v, const int src) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), src)); }
+
+// one flag bit per support row from the records of `frames` frames of N rows (stride floats per record, flag at float `off`):
+// thread = row, a wave's ballot = two words; bw words per frame
+__global__ __launch_bounds__(256) void kp_pack_bits_kernel(const float *recs, int stride, int off, int N, int bw, uint32_t *bits) {
+    const int n = blockIdx.x * 256 + threadIdx.x, f = blockIdx.y;
+    const bool flag = n < N && recs[((size_t)f * N + n) * stride + off] != 0.f;
+    const unsigned long long m = __ballot(flag);
+    const int w = n >> 5, lane = threadIdx.x & 63;
+    if ((lane & 31) == 0 && w < bw) bits[(size_t)f * bw + w] = (uint32_t)(m >> lane);
+}
 
 // VEC = contiguous channels one lane loads per neighbour (1, 2 or 4 -> dword / dwordx2 / dwordx4), NCH =
 // channel chunks of 16*VEC per pass.  MFMA column j of accumulator (ch, a) is channel
@@ -171,6 +228,11 @@ __device__ __forceinline__ KpQuery kp_query(const KpArgs &a, const int m, const 
     return q;
 }
 
+// what kp_prefix_done reads of a query, in scalar registers
+__device__ __forceinline__ KpStop kp_stop(const KpQuery &q) {
+    return {kp_scalar(2.0f * __builtin_amdgcn_sqrtf((q.qx * q.qx + q.qy * q.qy) + q.qz * q.qz)), kp_scalar(__builtin_amdgcn_sqrtf(q.rsup2)), q.rsup2};
+}
+
 // Stack mode: shift the support-side bases of a (a kernel's private copy) to the frame of query m (indices are frame-local).
 // REC: the support is a.recs, else a.s_pts / a.row_pos.
 template <bool REC>
@@ -214,8 +276,12 @@ __device__ __forceinline__ void kp_shadow(float4 *rec, const int nin) {
 // The aggregation of ONE query m by one wave (see the file header): acc[ch][v] = MFMA accumulators (rows = kernel points,
 // column j = channel c0 + ch*16*VEC + VEC*j + v), npos = neighbours whose feature row sums to > 0 (kpconv.py:113-114).
 // rec = the wave's private LDS record buffer (PHASE + KP_PAD entries); a is a private copy (frame shift).
-template <int VEC, int NCH, int PHASE, bool REC>
+// SORTED (needs REC): the staging of the sorted prefix only, see KpArgs.  ONE_PHASE: the caller guarantees H <= PHASE - without the
+// phase loop nothing of the staging is loop-carried, and the global-store kernels need 12 - 23 registers fewer than their unsorted forms
+// (the fused kernel keeps the loop: without it its 32-channel form spills).
+template <int VEC, int NCH, int PHASE, bool REC, bool SORTED = false, bool ONE_PHASE = false>
 __device__ __forceinline__ void kp_aggregate_query(KpArgs a, const int m, const int c0, float4 *rec, f32x4 (&acc)[NCH][VEC], int &npos) {
+    static_assert(REC || !SORTED, "the sorted form stages from records");
     constexpr int KP_PHASE = PHASE;
     const int lane = threadIdx.x & 63;
     const int j = lane & 15;
@@ -238,8 +304,9 @@ __device__ __forceinline__ void kp_aggregate_query(KpArgs a, const int m, const 
     }
     const char *fbase = reinterpret_cast<const char *>(a.feats);
     const unsigned ldfb = 4u * a.ldf;
+    [[maybe_unused]] bool done = false;   // SORTED: the row's survivors are all staged (wave-uniform)
 
-    for (int h0 = 0; h0 < a.H; h0 += KP_PHASE) {
+    for (int h0 = 0; h0 < (ONE_PHASE ? 1 : a.H); h0 += KP_PHASE) {
         const int nh = a.H - h0 < KP_PHASE ? a.H - h0 : KP_PHASE;  // multiple of 4
         // ---- stage the records of this phase: lane = neighbour; all index loads first, then all gathers
         int idr[KP_PHASE / 64];
@@ -249,19 +316,57 @@ __device__ __forceinline__ void kp_aggregate_query(KpArgs a, const int m, const 
             idr[r] = irow[h0 + (hl < nh ? hl : 0)];
             if (hl >= nh) idr[r] = a.N;
         }
-        float px[KP_PHASE / 64], py[KP_PHASE / 64], pz[KP_PHASE / 64];
-        int pos[KP_PHASE / 64];
-#pragma unroll
-        for (int r = 0; r < KP_PHASE / 64; ++r) kp_support<REC>(a, (unsigned)idr[r] < (unsigned)a.N ? idr[r] : 0, px[r], py[r], pz[r], pos[r]);
         int nin = 0;   // neighbours of this phase inside the kernel's support (wave-uniform)
+        if constexpr (SORTED) {
+            const KpStop stop = kp_stop(q);   // per phase, not across the step loop: it then costs the loop no registers
+            const uint32_t *bits = kp_bits(a, m);   // (the frame shift leaves row_pos alone)
+            unsigned fw[KP_PHASE / 64];   // the flag words of all neighbours: a few cache lines per wave, L1-resident
 #pragma unroll
-        for (int r = 0; r < KP_PHASE / 64; ++r) {
-            const bool valid = (unsigned)idr[r] < (unsigned)a.N;
-            npos += __popcll(__ballot(valid && pos[r] != 0));   // kpconv.py:113-115 counts over ALL neighbours
-            // kpconv.py:93: neighbours centred on the query
-            const float dx = px[r] - q.qx, dy = py[r] - q.qy, dz = pz[r] - q.qz;
-            const bool inside = valid && (dx * dx + dy * dy) + dz * dz < q.rsup2;
-            nin = kp_compact(rec, nin, inside, make_float4(dx, dy, dz, __int_as_float(idr[r])));
+            for (int r = 0; r < KP_PHASE / 64; ++r) fw[r] = bits[(unsigned)idr[r] < (unsigned)a.N ? idr[r] >> 5 : 0];
+#pragma unroll
+            for (int r = 0; r < KP_PHASE / 64; ++r) {
+                const bool valid = (unsigned)idr[r] < (unsigned)a.N;
+                const unsigned long long vm = __ballot(valid);
+                npos += __popcll(__ballot(valid && ((fw[r] >> (idr[r] & 31)) & 1u)));   // kpconv.py:113-115 counts over ALL neighbours
+                if (!done && vm != 0) {   // wave-uniform
+                    const int idc = valid ? idr[r] : 0;
+                    float px = 0.f, py = 0.f, pz = 0.f;
+                    int pos;
+                    bool got = true;   // this lane's record is gathered
+                    if (r == 0 && h0 == 0) {   // the row's first 16 neighbours, then - only if something behind them can be inside - the rest
+                        got = lane < 16;
+                        if (got) kp_support<REC>(a, idc, px, py, pz, pos);
+                        const float ex = px - q.qx, ey = py - q.qy, ez = pz - q.qz;
+                        done = !((vm >> 15) & 1) || kp_prefix_done(kp_lane_value((ex * ex + ey * ey) + ez * ez, 15), stop);
+                        if (!done) {
+                            if (!got) kp_support<REC>(a, idc, px, py, pz, pos);
+                            got = true;
+                        }
+                    } else {
+                        kp_support<REC>(a, idc, px, py, pz, pos);
+                    }
+                    // kpconv.py:93: neighbours centred on the query
+                    const float dx = px - q.qx, dy = py - q.qy, dz = pz - q.qz;
+                    const float d2 = (dx * dx + dy * dy) + dz * dz;
+                    const bool inside = valid && got && d2 < q.rsup2;
+                    nin = kp_compact(rec, nin, inside, make_float4(dx, dy, dz, __int_as_float(idr[r])));
+                    if (!done) done = !((vm >> 63) & 1) || kp_prefix_done(kp_lane_value(d2, 63), stop);
+                }
+            }
+        } else {
+            float px[KP_PHASE / 64], py[KP_PHASE / 64], pz[KP_PHASE / 64];
+            int pos[KP_PHASE / 64];
+#pragma unroll
+            for (int r = 0; r < KP_PHASE / 64; ++r) kp_support<REC>(a, (unsigned)idr[r] < (unsigned)a.N ? idr[r] : 0, px[r], py[r], pz[r], pos[r]);
+#pragma unroll
+            for (int r = 0; r < KP_PHASE / 64; ++r) {
+                const bool valid = (unsigned)idr[r] < (unsigned)a.N;
+                npos += __popcll(__ballot(valid && pos[r] != 0));   // kpconv.py:113-115 counts over ALL neighbours
+                // kpconv.py:93: neighbours centred on the query
+                const float dx = px[r] - q.qx, dy = py[r] - q.qy, dz = pz[r] - q.qz;
+                const bool inside = valid && (dx * dx + dy * dy) + dz * dz < q.rsup2;
+                nin = kp_compact(rec, nin, inside, make_float4(dx, dy, dz, __int_as_float(idr[r])));
+            }
         }
         kp_shadow(rec, nin);
         __builtin_amdgcn_wave_barrier();
@@ -344,7 +449,7 @@ __device__ __forceinline__ void kp_store(const KpArgs &a, const int m, const int
 
 // amdgpu_waves_per_eu: the occupancy each form had before the step loop got its wave-uniform branches - left alone, the register
 // allocator answers them with a second copy of the accumulators and loses a wave per SIMD (profiles/kpconv_records/README.md).
-template <int VEC, int NCH, bool REC>
+template <int VEC, int NCH, bool REC, bool SORTED = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(VEC * NCH == 8 ? 4 : (VEC * NCH == 4 ? 6 : 8)))) void kpconv_aggregate_kernel(KpArgs a) {
     __shared__ float4 rec_s[4][KP_PHASE_DEFAULT + KP_PAD];
     const int wv = threadIdx.x >> 6;
@@ -355,7 +460,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(VEC * NCH =
     const int c0 = blockIdx.y * (16 * VEC * NCH);
     f32x4 acc[NCH][VEC];
     int npos;
-    kp_aggregate_query<VEC, NCH, KP_PHASE_DEFAULT, REC>(a, m, c0, rec_s[wv], acc, npos);
+    kp_aggregate_query<VEC, NCH, KP_PHASE_DEFAULT, REC, SORTED, SORTED>(a, m, c0, rec_s[wv], acc, npos);   // sorted: the host sends H <= 128
     kp_store<VEC, NCH, true>(a, m, c0, acc, npos, blockIdx.y == 0);
 }
 
@@ -432,6 +537,8 @@ __global__ void kp_pack_c4_kernel(const float *feats, int ldf, int C, const floa
     out[2 * (size_t)i + 1] = make_float4(p[0], p[1], p[2], sum > 0.0f ? 1.0f : 0.0f);
 }
 
+// SORTED: the two halves of a record are gathered for the sorted prefix of the row only, the flags come from a.bits (see KpArgs).
+template <bool SORTED>
 __global__ __launch_bounds__(256) void kpconv_aggregate_c4_kernel(KpArgs a) {   // a.feats = packed records (N, 8)
     constexpr int PH = 128;
     __shared__ float4 rec_s[4][PH + 4];   // + one step of shadow records behind the compacted list
@@ -449,6 +556,7 @@ __global__ __launch_bounds__(256) void kpconv_aggregate_c4_kernel(KpArgs a) {   
     float4 *rec = rec_s[wv], *fea = fea_s[wv];
     const float fmask = j < a.C ? 1.0f : 0.0f;           // MFMA columns past C multiply zeros
     const float *fsel = reinterpret_cast<const float *>(fea) + (j & 3);
+    [[maybe_unused]] bool done = false;   // SORTED: the row's survivors are all staged (wave-uniform)
     for (int h0 = 0; h0 < a.H; h0 += PH) {
         const int nh = a.H - h0 < PH ? a.H - h0 : PH;    // multiple of 4
         int idr[2];
@@ -457,28 +565,71 @@ __global__ __launch_bounds__(256) void kpconv_aggregate_c4_kernel(KpArgs a) {   
             const int hl = r * 64 + lane;
             idr[r] = hl < nh ? irow[h0 + hl] : a.N;
         }
-        float4 fr[2], pp[2];
-#pragma unroll
-        for (int r = 0; r < 2; ++r) {
-            const int idc = (unsigned)idr[r] < (unsigned)a.N ? idr[r] : 0;
-            fr[r] = recs[2 * (size_t)idc];
-            pp[r] = recs[2 * (size_t)idc + 1];
-        }
         int nin = 0;
+        if constexpr (SORTED) {
+            const uint32_t *bits = kp_bits(a, m);
+            const KpStop stop = kp_stop(q);
+            unsigned fw[2];
 #pragma unroll
-        for (int r = 0; r < 2; ++r) {
-            const bool valid = (unsigned)idr[r] < (unsigned)a.N;
-            npos += __popcll(__ballot(valid && pp[r].w != 0.f));
-            const float dx = pp[r].x - q.qx, dy = pp[r].y - q.qy, dz = pp[r].z - q.qz;
-            const bool inside = valid && (dx * dx + dy * dy) + dz * dz < q.rsup2;
-            // kp_compact writes one array; two calls cost this kernel registers and instructions, so its two-array compaction stays here
-            const unsigned long long msk = __ballot(inside);
-            if (inside) {
-                const int slot = nin + __popcll(msk & ((1ull << lane) - 1ull));
-                rec[slot] = make_float4(dx, dy, dz, 0.f);
-                fea[slot] = fr[r];
+            for (int r = 0; r < 2; ++r) fw[r] = bits[(unsigned)idr[r] < (unsigned)a.N ? idr[r] >> 5 : 0];
+#pragma unroll
+            for (int r = 0; r < 2; ++r) {
+                const bool valid = (unsigned)idr[r] < (unsigned)a.N;
+                const unsigned long long vm = __ballot(valid);
+                npos += __popcll(__ballot(valid && ((fw[r] >> (idr[r] & 31)) & 1u)));
+                if (!done && vm != 0) {   // wave-uniform
+                    const size_t idc = valid ? idr[r] : 0;
+                    float4 f = make_float4(0.f, 0.f, 0.f, 0.f), p = f;
+                    bool got = true;
+                    if (r == 0 && h0 == 0) {   // the row's first 16 neighbours, then - only if something behind them can be inside - the rest
+                        got = lane < 16;
+                        if (got) { f = recs[2 * idc]; p = recs[2 * idc + 1]; }
+                        const float ex = p.x - q.qx, ey = p.y - q.qy, ez = p.z - q.qz;
+                        done = !((vm >> 15) & 1) || kp_prefix_done(kp_lane_value((ex * ex + ey * ey) + ez * ez, 15), stop);
+                        if (!done) {
+                            if (!got) { f = recs[2 * idc]; p = recs[2 * idc + 1]; }
+                            got = true;
+                        }
+                    } else {
+                        f = recs[2 * idc];
+                        p = recs[2 * idc + 1];
+                    }
+                    const float dx = p.x - q.qx, dy = p.y - q.qy, dz = p.z - q.qz;
+                    const float d2 = (dx * dx + dy * dy) + dz * dz;
+                    const bool inside = valid && got && d2 < q.rsup2;
+                    const unsigned long long msk = __ballot(inside);   // the two-array compaction of the unsorted form
+                    if (inside) {
+                        const int slot = nin + __popcll(msk & ((1ull << lane) - 1ull));
+                        rec[slot] = make_float4(dx, dy, dz, 0.f);
+                        fea[slot] = f;
+                    }
+                    nin += __popcll(msk);
+                    if (!done) done = !((vm >> 63) & 1) || kp_prefix_done(kp_lane_value(d2, 63), stop);
+                }
             }
-            nin += __popcll(msk);
+        } else {
+            float4 fr[2], pp[2];
+#pragma unroll
+            for (int r = 0; r < 2; ++r) {
+                const int idc = (unsigned)idr[r] < (unsigned)a.N ? idr[r] : 0;
+                fr[r] = recs[2 * (size_t)idc];
+                pp[r] = recs[2 * (size_t)idc + 1];
+            }
+#pragma unroll
+            for (int r = 0; r < 2; ++r) {
+                const bool valid = (unsigned)idr[r] < (unsigned)a.N;
+                npos += __popcll(__ballot(valid && pp[r].w != 0.f));
+                const float dx = pp[r].x - q.qx, dy = pp[r].y - q.qy, dz = pp[r].z - q.qz;
+                const bool inside = valid && (dx * dx + dy * dy) + dz * dz < q.rsup2;
+                // kp_compact writes one array; two calls cost this kernel registers and instructions, so its two-array compaction stays here
+                const unsigned long long msk = __ballot(inside);
+                if (inside) {
+                    const int slot = nin + __popcll(msk & ((1ull << lane) - 1ull));
+                    rec[slot] = make_float4(dx, dy, dz, 0.f);
+                    fea[slot] = fr[r];
+                }
+                nin += __popcll(msk);
+            }
         }
         if (lane < 4) {   // the last step is filled up with shadow neighbours: influence exactly 0, zero features
             rec[nin + lane] = make_float4(1e18f, 0.f, 0.f, 0.f);
@@ -536,7 +687,7 @@ struct KpFusedArgs {
     int qt;                         // queries per workgroup = rows per statistics slab: 16, 32 or 64
 };
 
-template <int MID, int PHASE, bool RECS>
+template <int MID, int PHASE, bool RECS, bool SORTED = false>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) void kpconv_fused_kernel(KpFusedArgs fa) {   // two workgroups per CU
 
     constexpr int VEC = MID / 16, K = 15 * MID, KLD = K + 8, NT = MID / 16, KQ = 8 / NT, KSTEPS = K / 32;
@@ -575,7 +726,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
             m = __builtin_amdgcn_readfirstlane(m);
             f32x4 acc[1][VEC];
             int npos;
-            kp_aggregate_query<VEC, 1, PHASE, RECS>(fa.a, m, 0, rec_s[wv], acc, npos);
+            kp_aggregate_query<VEC, 1, PHASE, RECS, SORTED>(fa.a, m, 0, rec_s[wv], acc, npos);
             // D layout 16x16: row (kernel point) = 4 g + r, column j -> channels VEC j .. VEC j + VEC - 1 of tile row ql
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
@@ -796,13 +947,15 @@ static int kp_check_support(int N, int ldf) {
 }
 
 // Shape checks and kernel choice of the aggregation; REC: the support arrives as 16-byte records (a.recs) instead of a.s_pts / a.row_pos.
-template <bool REC>
+template <bool REC, bool SORTED = false>
 static int kp_aggregate_launch(const KpArgs &a, int agg_planes, int frames, cofi_stream_t stream) {
     const int N = a.N, C = a.C, M = a.M, H = a.H, ldf = a.ldf, ld_agg = a.ld_agg;   // M: the queries of all frames
     if (N <= 0 || C <= 0 || a.Mpf < 0 || H <= 0 || (H & 3) || ldf < C || ld_agg < 15 * C || !(a.sigma > 0.f) || frames <= 0) return COFI_EINVAL;
     if (agg_planes && ((ld_agg & 7) || (C & 3) || ((uintptr_t)a.agg & 15))) return COFI_EINVAL;
     if (int rc = kp_check_support(N, ldf)) return rc;
     if (M == 0) return 0;
+    if constexpr (SORTED)
+        if (H > KP_PHASE_DEFAULT) return kp_aggregate_launch<REC, false>(a, agg_planes, frames, stream);   // the sorted kernels stage one phase
     hipStream_t s = cofi_s(stream);
     const int mb = cofi_cdiv(M, 4);
     if ((C == 256 || C == 512) && (ldf & 3) == 0 && H <= 128 && M % (C == 256 ? 2 : 1) == 0) {
@@ -812,13 +965,13 @@ static int kp_aggregate_launch(const KpArgs &a, int agg_planes, int frames, cofi
             hipLaunchKernelGGL((kpconv_aggregate_shared_kernel<4, REC>), dim3(M), dim3(256), 0, s, a);
     } else if ((C & 3) == 0 && (ldf & 3) == 0 && C >= 64) {
         if (C % 128 == 0)
-            hipLaunchKernelGGL((kpconv_aggregate_kernel<4, 2, REC>), dim3(mb, C / 128), dim3(256), 0, s, a);
+            hipLaunchKernelGGL((kpconv_aggregate_kernel<4, 2, REC, SORTED>), dim3(mb, C / 128), dim3(256), 0, s, a);
         else
-            hipLaunchKernelGGL((kpconv_aggregate_kernel<4, 1, REC>), dim3(mb, cofi_cdiv(C, 64)), dim3(256), 0, s, a);
+            hipLaunchKernelGGL((kpconv_aggregate_kernel<4, 1, REC, SORTED>), dim3(mb, cofi_cdiv(C, 64)), dim3(256), 0, s, a);
     } else if ((C & 1) == 0 && (ldf & 1) == 0 && C >= 32) {
-        hipLaunchKernelGGL((kpconv_aggregate_kernel<2, 1, REC>), dim3(mb, cofi_cdiv(C, 32)), dim3(256), 0, s, a);
+        hipLaunchKernelGGL((kpconv_aggregate_kernel<2, 1, REC, SORTED>), dim3(mb, cofi_cdiv(C, 32)), dim3(256), 0, s, a);
     } else {
-        hipLaunchKernelGGL((kpconv_aggregate_kernel<1, 1, REC>), dim3(mb, cofi_cdiv(C, 16)), dim3(256), 0, s, a);
+        hipLaunchKernelGGL((kpconv_aggregate_kernel<1, 1, REC, SORTED>), dim3(mb, cofi_cdiv(C, 16)), dim3(256), 0, s, a);
     }
     return cofi_launch_status();
 }
@@ -842,6 +995,35 @@ extern "C" int cofi_kpconv_aggregate_rec(const float *feats, int ldf, int N, int
                                              cnt, frames, order), agg_planes, frames, stream);
 }
 
+// The flag bits of the SORTED forms from records of `stride` floats whose last float is the flag (4: support records, 8: first-layer
+// records): (frames, cofi_kp_bits_words(N)) 32-bit words, bit n & 31 of word n >> 5 of a frame = flag of its row n, padding bits 0.
+extern "C" int cofi_kp_bits_words(int N) { return N > 0 ? cofi_cdiv(N, 32) : 0; }
+
+extern "C" int cofi_kp_pack_bits(const float *records, int stride, int N, int frames, uint32_t *bits, cofi_stream_t stream) {
+    if (!records || !bits || N <= 0 || frames <= 0 || (stride != 4 && stride != 8)) return COFI_EINVAL;
+    hipLaunchKernelGGL(kp_pack_bits_kernel, dim3(cofi_cdiv(N, 256), frames), dim3(256), 0, cofi_s(stream), records, stride, stride - 1, N,
+                       cofi_kp_bits_words(N), bits);
+    return cofi_launch_status();
+}
+
+// a with the flag bits of its N rows per frame in the place of row_pos (see KpArgs)
+static KpArgs kp_with_bits(KpArgs a, const uint32_t *bits) {
+    a.row_pos = reinterpret_cast<const uint8_t *>(bits);
+    return a;
+}
+
+// cofi_kpconv_aggregate_rec for index tables whose rows are sorted (see KpArgs): the records of a row's sorted prefix are gathered,
+// the flags of all its neighbours come from `bits` (cofi_kp_pack_bits of these records).  Same results, bit for bit, on every sorted
+// table; undefined on any other.  The wide layers (C = 256 / 512) run cofi_kpconv_aggregate_rec's kernel.
+extern "C" int cofi_kpconv_aggregate_rec_sorted(const float *feats, int ldf, int N, int C, const float *q_pts, const float *records,
+                                                const uint32_t *bits, const int32_t *idx, int M, int H, const float *kernel_points, float sigma,
+                                                float *agg, int ld_agg, int agg_planes, float *cnt, int frames, const int32_t *order,
+                                                cofi_stream_t stream) {
+    if (!feats || !q_pts || !records || !bits || !idx || !kernel_points || !agg || !cnt || ((uintptr_t)records & 15)) return COFI_EINVAL;
+    return kp_aggregate_launch<true, true>(kp_with_bits(kp_args(feats, ldf, N, C, q_pts, nullptr, nullptr, records, idx, M, H, kernel_points, sigma, agg,
+                                                                ld_agg, agg_planes, cnt, frames, order), bits), agg_planes, frames, stream);
+}
+
 // First-layer form (C <= 4): pack [features | position | positive-sum flag] into 32-byte records once, then aggregate from them.
 extern "C" int cofi_kp_pack_c4(const float *feats, int ldf, int C, const float *points, int N, float *records, cofi_stream_t stream) {
     if (!feats || !points || !records || N <= 0 || C <= 0 || C > 4 || ldf < C || ((uintptr_t)records & 15)) return COFI_EINVAL;
@@ -849,15 +1031,35 @@ extern "C" int cofi_kp_pack_c4(const float *feats, int ldf, int C, const float *
     return cofi_launch_status();
 }
 
-extern "C" int cofi_kpconv_aggregate_c4(const float *records, int N, int C, const float *q_pts, const int32_t *idx, int M, int H,
-                                        const float *kernel_points, float sigma, float *agg, int ld_agg, float *cnt, int frames,
-                                        const int32_t *order, cofi_stream_t stream) {
+// bits: the SORTED form with these flag bits, nullptr: the unsorted form
+static int kp_c4_launch(const float *records, const uint32_t *bits, int N, int C, const float *q_pts, const int32_t *idx, int M, int H,
+                        const float *kernel_points, float sigma, float *agg, int ld_agg, float *cnt, int frames, const int32_t *order,
+                        cofi_stream_t stream) {
     if (!records || !q_pts || !idx || !kernel_points || !agg || !cnt || ((uintptr_t)records & 15)) return COFI_EINVAL;
     if (N <= 0 || C <= 0 || C > 4 || M < 0 || H <= 0 || (H & 3) || ld_agg < 15 * C || !(sigma > 0.f) || frames <= 0) return COFI_EINVAL;
     if (M == 0) return 0;
-    const KpArgs a = kp_args(records, 8, N, C, q_pts, nullptr, nullptr, nullptr, idx, M, H, kernel_points, sigma, agg, ld_agg, 0, cnt, frames, order);
-    hipLaunchKernelGGL(kpconv_aggregate_c4_kernel, dim3(cofi_cdiv((long)M * frames, 4)), dim3(256), 0, cofi_s(stream), a);
+    const KpArgs a = kp_with_bits(kp_args(records, 8, N, C, q_pts, nullptr, nullptr, nullptr, idx, M, H, kernel_points, sigma, agg, ld_agg, 0, cnt,
+                                          frames, order), bits);
+    const dim3 grid(cofi_cdiv((long)M * frames, 4));
+    if (bits)
+        hipLaunchKernelGGL(kpconv_aggregate_c4_kernel<true>, grid, dim3(256), 0, cofi_s(stream), a);
+    else
+        hipLaunchKernelGGL(kpconv_aggregate_c4_kernel<false>, grid, dim3(256), 0, cofi_s(stream), a);
     return cofi_launch_status();
+}
+
+extern "C" int cofi_kpconv_aggregate_c4(const float *records, int N, int C, const float *q_pts, const int32_t *idx, int M, int H,
+                                        const float *kernel_points, float sigma, float *agg, int ld_agg, float *cnt, int frames,
+                                        const int32_t *order, cofi_stream_t stream) {
+    return kp_c4_launch(records, nullptr, N, C, q_pts, idx, M, H, kernel_points, sigma, agg, ld_agg, cnt, frames, order, stream);
+}
+
+// cofi_kpconv_aggregate_c4 for sorted index tables, bits = cofi_kp_pack_bits(records, 8, ...): see cofi_kpconv_aggregate_rec_sorted
+extern "C" int cofi_kpconv_aggregate_c4_sorted(const float *records, const uint32_t *bits, int N, int C, const float *q_pts, const int32_t *idx, int M,
+                                               int H, const float *kernel_points, float sigma, float *agg, int ld_agg, float *cnt, int frames,
+                                               const int32_t *order, cofi_stream_t stream) {
+    if (!bits) return COFI_EINVAL;
+    return kp_c4_launch(records, bits, N, C, q_pts, idx, M, H, kernel_points, sigma, agg, ld_agg, cnt, frames, order, stream);
 }
 
 // rows per statistics slab (= queries per workgroup) the fused kernel uses for M queries per frame: the largest of 64 / 32 / 16 that
@@ -869,7 +1071,7 @@ extern "C" int cofi_kpconv_fused_slab_rows(int C, int M, int frames) {
     return 16;
 }
 
-template <bool REC>
+template <bool REC, bool SORTED = false>
 static int kp_fused_launch(const KpArgs &a, const void *w_planes, int ldw, const float *bias, float *y, int ldy, float *colpart, int stat_width,
                            int frames, cofi_stream_t stream) {
     const int N = a.N, C = a.C, M = a.Mpf, ldf = a.ldf;
@@ -890,9 +1092,9 @@ static int kp_fused_launch(const KpArgs &a, const void *w_planes, int ldw, const
     fa.ldw = ldw; fa.bias = bias; fa.y = y; fa.ldy = ldy; fa.colpart = colpart; fa.stat_shift = shift; fa.qt = qt;
     const int nwg = (int)((long)M * frames / qt);
     if (C == 64)
-        hipLaunchKernelGGL((kpconv_fused_kernel<64, 64, REC>), dim3(nwg), dim3(512), 0, cofi_s(stream), fa);
+        hipLaunchKernelGGL((kpconv_fused_kernel<64, 64, REC, SORTED>), dim3(nwg), dim3(512), 0, cofi_s(stream), fa);
     else
-        hipLaunchKernelGGL((kpconv_fused_kernel<32, 128, REC>), dim3(nwg), dim3(512), 0, cofi_s(stream), fa);
+        hipLaunchKernelGGL((kpconv_fused_kernel<32, 128, REC, SORTED>), dim3(nwg), dim3(512), 0, cofi_s(stream), fa);
     return cofi_launch_status();
 }
 
@@ -911,6 +1113,17 @@ extern "C" int cofi_kpconv_fused_rec(const float *feats, int ldf, int N, int C, 
     if (!feats || !q_pts || !records || !idx || !kernel_points || !w_planes || !y || ((uintptr_t)records & 15)) return COFI_EINVAL;
     return kp_fused_launch<true>(kp_args(feats, ldf, N, C, q_pts, nullptr, nullptr, records, idx, M, H, kernel_points, sigma, nullptr, 0, 0, nullptr, frames,
                                          order), w_planes, ldw, bias, y, ldy, colpart, stat_width, frames, stream);
+}
+
+// cofi_kpconv_fused_rec for sorted index tables (see cofi_kpconv_aggregate_rec_sorted)
+extern "C" int cofi_kpconv_fused_rec_sorted(const float *feats, int ldf, int N, int C, const float *q_pts, const float *records, const uint32_t *bits,
+                                            const int32_t *idx, int M, int H, const float *kernel_points, float sigma, const void *w_planes, int ldw,
+                                            const float *bias, float *y, int ldy, float *colpart, int stat_width, int frames, const int32_t *order,
+                                            cofi_stream_t stream) {
+    if (!feats || !q_pts || !records || !bits || !idx || !kernel_points || !w_planes || !y || ((uintptr_t)records & 15)) return COFI_EINVAL;
+    return kp_fused_launch<true, true>(kp_with_bits(kp_args(feats, ldf, N, C, q_pts, nullptr, nullptr, records, idx, M, H, kernel_points, sigma, nullptr, 0,
+                                                            0, nullptr, frames, order), bits), w_planes, ldw, bias, y, ldy, colpart, stat_width, frames,
+                                       stream);
 }
 
 extern "C" int cofi_neighbor_maxpool(const float *x, int ldx, int N, int C, const int32_t *idx, int M, int H, float *out, int ldo,

@@ -34,6 +34,13 @@ DECODER_UP = {"decoder4": 2048, "decoder3": 1024, "decoder2": 512}   # columns o
 # leaves CUs idle, which the one larger contraction of the concat form does not; 256 tiles = 8192 coarse rows = 16384 rows here.
 # decoder4 and decoder2 win at every measured size.
 DECODER_PROJECT_MIN_ROWS = {"decoder3": 16384}
+# Sorted neighbour tables (the pyramid key "sorted_tables"): the KPConv layers up to this many aggregated channels run the sorted
+# aggregation kernels (record gathers for a row's sorted prefix only, ops.kpconv_prefix).  Measured per layer on MI355X
+# (profiles/kpconv_prefix/README.md): 4 / 32 / 64 channels - 2 - 5 of 128 neighbours inside the support, the staging is what a query
+# costs - gain 8 - 23 %; at 128 channels (8 inside, the 15 x 128 result row dominates) the sorted form is +0.5 % - outside the parent's
+# spread on two of three layers - and the wide layers' kernel stages through NP waves and has no sorted form: those keep the unsorted
+# kernels and are not charged the launch that writes the flag bits.
+PREFIX_MAX_CHANNELS = 64
 
 
 def decoder_weight_unused(key: str) -> bool:
@@ -113,7 +120,7 @@ def _stats(y, part, frames: int, width: int = 1):
     return ops.ColStats(part, y.shape[0], GN_GROUPS, frames, width=width)
 
 
-def _kpconv(P, p: str, feats, q_pts, s_pts, idx, sigma: float, frames: int = 1, order=None):
+def _kpconv(P, p: str, feats, q_pts, s_pts, idx, sigma: float, frames: int = 1, order=None, sorted_tables: bool = False):
     """-> (KPConv output, its GroupNorm statistics).  The statistics come out of the producing kernel's epilogue (partials per
     slab and group) instead of another pass over the activation.  Aggregate + GEMM; with COFI_KPCONV_FUSED=1 the narrow layers
     (32 / 64 channels in = out) run as ONE kernel and the (M, 15 C) aggregate never reaches memory (slower, see FUSED_KPCONV)."""
@@ -122,11 +129,12 @@ def _kpconv(P, p: str, feats, q_pts, s_pts, idx, sigma: float, frames: int = 1, 
     C = feats.shape[1]
     if FUSED_KPCONV and isinstance(w, ops.SplitW) and w.shape[0] == C and ops.kpconv_fused_slab_rows(C, idx.shape[0] // frames, frames):
         y, part, sr = ops.kpconv_fused(feats, q_pts, s_pts, idx, P[p + "KPConv.kernel_points"], sigma, w, P[p + "KPConv.bias"], stat_width=sw,
-                                       frames=frames, order=order)
+                                       frames=frames, order=order, sorted_tables=sorted_tables)
         return y, ops.ColStats(part, y.shape[0], GN_GROUPS, frames, width=sw, slab_rows=sr)
     planes = (ops.gemm_mode() == "bf16x3" and isinstance(w, ops.SplitW)
               and (AGG_PLANES == "all" or (AGG_PLANES not in ("0", "off") and frames >= AGG_PLANES_MIN_FRAMES)))
-    agg, cnt = ops.kpconv_aggregate(feats, q_pts, s_pts, idx, P[p + "KPConv.kernel_points"], sigma, frames=frames, order=order, planes=planes)
+    agg, cnt = ops.kpconv_aggregate(feats, q_pts, s_pts, idx, P[p + "KPConv.kernel_points"], sigma, frames=frames, order=order, planes=planes,
+                                    sorted_tables=sorted_tables)
     y, part = ops.gemm_colstats(agg, w, bias=P[p + "KPConv.bias"], rowdiv=cnt, stat_width=sw)
     return y, _stats(y, part, frames, sw)
 
@@ -146,10 +154,11 @@ def _unary(P, p: str, x, slope: float, out=None, frames: int = 1, want_row_pos: 
                                 want_row_pos=want_row_pos, points=points)
 
 
-def run_block(P, blk: KPBlock, feats, q_pts, s_pts, idx, out=None, concurrent: bool = True, frames: int = 1, order=None):
+def run_block(P, blk: KPBlock, feats, q_pts, s_pts, idx, out=None, concurrent: bool = True, frames: int = 1, order=None,
+              sorted_tables: bool = False):
     p = "pc_encoder.%s." % blk.name
     if blk.kind == "conv":  # modules.py:155-159
-        y, st = _kpconv(P, p, feats, q_pts, s_pts, idx, blk.sigma, frames, order)
+        y, st = _kpconv(P, p, feats, q_pts, s_pts, idx, blk.sigma, frames, order, sorted_tables)
         return ops.group_norm_apply(y, st, P[p + "norm.norm.weight"], P[p + "norm.norm.bias"], slope=LRELU, out=out, frames=frames)
     # modules.py:222-240.  The shortcut (max-pool / Linear+GN statistics) only meets the main branch in the
     # final fused normalise+add+LeakyReLU: it runs on a side stream.
@@ -163,7 +172,7 @@ def run_block(P, blk: KPBlock, feats, q_pts, s_pts, idx, out=None, concurrent: b
     # stages per support row: the 16-byte record (position, positive-sum flag); the rows of unary1 are the support points
     # (a strided block: the finer stage's)
     x = _unary(P, p + "unary1.", feats, LRELU, frames=frames, want_row_pos=True, points=s_pts) if blk.cin != blk.mid else feats
-    y, st = _kpconv(P, p, x, q_pts, s_pts, idx, blk.sigma, frames, order)
+    y, st = _kpconv(P, p, x, q_pts, s_pts, idx, blk.sigma, frames, order, sorted_tables)
     # norm_conv + LeakyReLU (modules.py:232-233) is consumed by unary2's Linear only: applied by that GEMM's operand loader
     x = ops.Normed(y, st, P[p + "norm_conv.norm.weight"], P[p + "norm_conv.norm.bias"], LRELU)
     y2, st2 = _unary_raw(P, p + "unary2.", x, frames)
@@ -194,20 +203,21 @@ def _unary_plain(P, kind: str, p: str, x, slope: float, res=None, out=None):
     return _ln(P, p + "norm.", ops.gemm(x, w, bias=b), slope, res=res, out=out)
 
 
-def _kpconv_plain(P, kind: str, p: str, np_: str, feats, q_pts, s_pts, idx, sigma, frames, order, out=None):
-    agg, cnt = ops.kpconv_aggregate(feats, q_pts, s_pts, idx, P[p + "KPConv.kernel_points"], sigma, frames=frames, order=order)
+def _kpconv_plain(P, kind: str, p: str, np_: str, feats, q_pts, s_pts, idx, sigma, frames, order, out=None, sorted_tables: bool = False):
+    agg, cnt = ops.kpconv_aggregate(feats, q_pts, s_pts, idx, P[p + "KPConv.kernel_points"], sigma, frames=frames, order=order,
+                                    sorted_tables=sorted_tables)
     w, b = P[p + "KPConv.weights"], P[p + "KPConv.bias"]
     if kind == "bn":
         return ops.gemm(agg, w, bias=b, rowdiv=cnt, act=ops.ACT_LEAKY01, out=out)
     return _ln(P, np_, ops.gemm(agg, w, bias=b, rowdiv=cnt), LRELU, out=out)
 
 
-def run_block_plain(P, kind: str, blk: KPBlock, feats, q_pts, s_pts, idx, out=None, frames: int = 1, order=None):
+def run_block_plain(P, kind: str, blk: KPBlock, feats, q_pts, s_pts, idx, out=None, frames: int = 1, order=None, sorted_tables: bool = False):
     p = "pc_encoder.%s." % blk.name
     if blk.kind == "conv":   # modules.py:155-159
-        return _kpconv_plain(P, kind, p, p + "norm.", feats, q_pts, s_pts, idx, blk.sigma, frames, order, out=out)
+        return _kpconv_plain(P, kind, p, p + "norm.", feats, q_pts, s_pts, idx, blk.sigma, frames, order, out=out, sorted_tables=sorted_tables)
     x = _unary_plain(P, kind, p + "unary1.", feats, LRELU) if blk.cin != blk.mid else feats   # modules.py:222-240
-    x = _kpconv_plain(P, kind, p, p + "norm_conv.", x, q_pts, s_pts, idx, blk.sigma, frames, order)
+    x = _kpconv_plain(P, kind, p, p + "norm_conv.", x, q_pts, s_pts, idx, blk.sigma, frames, order, sorted_tables=sorted_tables)
     sc = ops.neighbor_maxpool(feats, idx, frames=frames, order=order) if blk.strided else feats
     if blk.has_shortcut_unary:
         sc = _unary_plain(P, kind, p + "unary_shortcut.", sc, 1.0)
@@ -230,8 +240,10 @@ def _decoder(P, kind: str, name: str, coarse, stage, up_idx, frames: int):
     return _ln(P, p + "norm.", ops.gemm(stage, w, bias=b, frames=frames, res=proj, res_idx=up_idx), LRELU)
 
 
-def run_fpn(P, points: List[torch.Tensor], neighbors, subsampling, upsampling, feats, taps=None, frames: int = 1, order=None, l2norm_fine: bool = False):
-    """`order` (optional): per stage, the frame-local processing order of the stage's points (spatially sorted)."""
+def run_fpn(P, points: List[torch.Tensor], neighbors, subsampling, upsampling, feats, taps=None, frames: int = 1, order=None, l2norm_fine: bool = False,
+            sorted_tables: bool = False):
+    """`order` (optional): per stage, the frame-local processing order of the stage's points (spatially sorted).  sorted_tables: the
+    caller's promise that the rows of `neighbors` and `subsampling` are sorted (the pyramid key "sorted_tables")."""
     """Returns [latent_s2 (N1,64), latent_s3 (N2,512), latent_s4 (N3,1024), feats_s5 (N4,2048)].
     The decoders (kp_backbone.py:111-124) run in the projected form (_decoder, DECODER_CONCAT above).  In the concat form the last
     block of stages 1..3 writes directly into the right part of the decoder's concat buffer (kp_backbone.py:112,117,122 torch.cat)."""
@@ -258,10 +270,12 @@ def run_fpn(P, points: List[torch.Tensor], neighbors, subsampling, upsampling, f
         if st in cat and last_of_stage[st] == blk.name:
             w = stage_width[st]
             out = cat[st][:, cat[st].shape[1] - w:]
+        srt = sorted_tables and (blk.cin if blk.kind == "conv" else blk.mid) <= PREFIX_MAX_CHANNELS
         if kind == "gn":
-            x = run_block(P, blk, x, q, s, idx, out=out, frames=frames, order=None if order is None else order[st])
+            x = run_block(P, blk, x, q, s, idx, out=out, frames=frames, order=None if order is None else order[st], sorted_tables=srt)
         else:
-            x = run_block_plain(P, kind, blk, x, q, s, idx, out=out, frames=frames, order=None if order is None else order[st])
+            x = run_block_plain(P, kind, blk, x, q, s, idx, out=out, frames=frames, order=None if order is None else order[st],
+                                sorted_tables=srt)
         stage_out[st] = x
         if taps is not None:
             taps[blk.name] = x

@@ -209,7 +209,7 @@ class CoFiI2P(nn.Module):
 
     # ------------------------------------------------------------------ device-side forward (no host sync)
     def _run_device(self, P, points, neighbors, subsampling, upsampling, feats, img, mode, fine_center_kpt_coors,
-                    fine_pc_inline_index, taps=None, order=None, pc_first: bool = False, cameras: int = 1):
+                    fine_pc_inline_index, taps=None, order=None, pc_first: bool = False, cameras: int = 1, sorted_tables: bool = False):
         """Everything of network.py:74-161 that runs on the device.  Test-mode outputs are sized at
         capacity (N4 rows) with the match count left in device memory: capturable in a hipGraph.
 
@@ -258,7 +258,8 @@ class CoFiI2P(nn.Module):
 
         def point_branch():   # network.py:76,83-84,107,111
             # F.normalize of the fine point descriptors (network.py:83) rides in decoder2's GEMM epilogue (taps: the raw decoder output is wanted)
-            pc_set_ = kpfpn.run_fpn(P, points, neighbors, subsampling, upsampling, feats, taps=taps, frames=S, order=order, l2norm_fine=taps is None)
+            pc_set_ = kpfpn.run_fpn(P, points, neighbors, subsampling, upsampling, feats, taps=taps, frames=S, order=order, l2norm_fine=taps is None,
+                                    sorted_tables=sorted_tables)
             fine_pc_ = pc_set_[0] if taps is None else ops.l2norm_rows(pc_set_[0])  # (S*N1,64)
             # a rig: the tokens of the S clouds are made once, then copied in front of each of the cloud's cameras
             tok = ts.pc[0] if cameras == 1 else torch.empty((S * N4, D_MODEL), dtype=torch.float32, device=dev)
@@ -383,7 +384,7 @@ class CoFiI2P(nn.Module):
         return self
 
     def _graph_forward(self, P, points, neighbors, subsampling, upsampling, feats, img, mode, kpt, inl, slot: int = 0,
-                       branch_mask: int = 7, order=None, inputs_stable: bool = False, cameras: int = 1):
+                       branch_mask: int = 7, order=None, inputs_stable: bool = False, cameras: int = 1, sorted_tables: bool = False):
         def sig(t):
             if t is None:
                 return None
@@ -397,7 +398,8 @@ class CoFiI2P(nn.Module):
         tensors = list(points) + list(neighbors) + list(subsampling) + list(upsampling) + order + [feats, img, kpt, inl]
         # everything a captured launch sequence depends on besides the tensor signature: arithmetic, optional branches
         key = ("stable" if inputs_stable else "copy", mode, str(img.device), slot, branch_mask, ops.gemm_mode(), ops.f16x3_big(), self.compute_unused_image_maps,
-               transformer.JOINT_SELF, transformer.FUSED_CHAIN, transformer.TAIL_MAX_ROWS, kpfpn.FUSED_KPCONV, kpfpn.AGG_PLANES, cameras) + tuple(sig(t) for t in tensors)
+               transformer.JOINT_SELF, transformer.FUSED_CHAIN, transformer.TAIL_MAX_ROWS, kpfpn.FUSED_KPCONV, kpfpn.AGG_PLANES, cameras,
+               bool(sorted_tables) and ops.kpconv_prefix()) + tuple(sig(t) for t in tensors)
         saved_mask, saved_slot = ops.BRANCH_MASK, ops.Workspace.slot
         ops.set_workspace_slot(slot)
         ops.BRANCH_MASK = branch_mask  # which intra-frame forks the capture records
@@ -422,7 +424,7 @@ class CoFiI2P(nn.Module):
                 o = [0, n[0], n[0] + n[1], n[0] + n[1] + n[2], n[0] + n[1] + n[2] + n[3], sum(n)]
                 args = (static[o[0]:o[1]], static[o[1]:o[2]], static[o[2]:o[3]], static[o[3]:o[4]], static[o[5]], static[o[5] + 1], mode,
                         static[o[5] + 2], static[o[5] + 3], None, (static[o[4]:o[5]] or None),
-                        ALTERNATE_ORDER and branch_mask == 0 and bool(slot & 1), cameras)
+                        ALTERNATE_ORDER and branch_mask == 0 and bool(slot & 1), cameras, bool(sorted_tables))
                 # warm-up AND capture run on one persistent stream, so every per-stream workspace is grown (in the
                 # ordinary allocator pool) before the capture starts and nothing is allocated for it inside
                 if getattr(self, "_capture_stream", None) is None or self._capture_stream.device != img.device:
@@ -466,6 +468,8 @@ class CoFiI2P(nn.Module):
         out["feats"] = torch.cat([p["feats"] for p in pyramids], 0).contiguous()
         if all("order" in p for p in pyramids):
             out["order"] = [torch.cat([p["order"][i] for p in pyramids], 0).contiguous() for i in range(len(pyramids[0]["order"]))]
+        if all(p.get("sorted_tables") for p in pyramids):   # the promise of sorted neighbour rows holds for the stack only if every frame gives it
+            out["sorted_tables"] = True
         return out, torch.cat([im.reshape(1, *im.shape[-3:]) for im in imgs], 0).contiguous()
 
     def frame_streams(self, n: int, device=None):
@@ -644,7 +648,8 @@ class CoFiI2P(nn.Module):
         # fork/join only adds join latency then — measured 254 vs 331 frames/s at two frames in flight)
         outs = self._graph_forward(P, points, tabs[0], tabs[1], tabs[2], pc_data_dict["feats"].contiguous(), img.contiguous(), mode, None,
                                    None, slot=slot, branch_mask=self.async_branch_mask,
-                                   order=pc_data_dict.get("order"), inputs_stable=inputs_stable, cameras=cameras)
+                                   order=pc_data_dict.get("order"), inputs_stable=inputs_stable, cameras=cameras,
+                                   sorted_tables=bool(pc_data_dict.get("sorted_tables")))
         hosts = self.__dict__.setdefault("_count_host", {})   # one pinned landing buffer per slot (a slot is finished before it is reused)
         host = hosts.get((slot, len(outs)))
         if host is None:
@@ -710,7 +715,8 @@ class CoFiI2P(nn.Module):
             tabs = [[self._as_idx32(t) for t in pc_data_dict[k]] for k in ("neighbors", "subsampling", "upsampling")]
             outs = self._graph_forward(P, points, tabs[0], tabs[1], tabs[2], pc_data_dict["feats"].contiguous(), img.contiguous(), "val",
                                        labels[0], labels[1], slot=slot, branch_mask=self.async_branch_mask,
-                                       order=pc_data_dict.get("order"), inputs_stable=inputs_stable)
+                                       order=pc_data_dict.get("order"), inputs_stable=inputs_stable,
+                                       sorted_tables=bool(pc_data_dict.get("sorted_tables")))
         done = torch.cuda.Event()
         done.record()
         return {"out": outs, "done": done, "mode": "val"}
@@ -800,13 +806,14 @@ class CoFiI2P(nn.Module):
         upsampling = [self._as_idx32(t) for t in pc_data_dict["upsampling"]]
         feats = pc_data_dict["feats"].contiguous()
         order = pc_data_dict.get("order")  # optional: spatially sorted processing order per stage (preprocess.morton_order)
+        srt = bool(pc_data_dict.get("sorted_tables"))  # optional: the promise of sorted neighbour rows (preprocess.build_pyramid)
         auto = self._auto_graphs and not self._use_graphs and taps is None
         if (self._use_graphs or auto) and taps is None:
             o = self._graph_forward(P, points, neighbors, subsampling, upsampling, feats, img.contiguous(), mode, fine_center_kpt_coors,
-                                    fine_pc_inline_index, order=order)[0]
+                                    fine_pc_inline_index, order=order, sorted_tables=srt)[0]
         else:
             o = self._run_device(P, points, neighbors, subsampling, upsampling, feats, img, mode, fine_center_kpt_coors,
-                                 fine_pc_inline_index, taps=taps, order=order)[0]
+                                 fine_pc_inline_index, taps=taps, order=order, sorted_tables=srt)[0]
         own = (lambda t: t.clone() if torch.is_tensor(t) else t) if auto else (lambda t: t)   # unasked graphs: results the caller owns
         if mode in ("train", "val"):
             return tuple(own(t) for t in (o["img_desc"], o["pc_desc"], o["img_score"], o["pc_score"], o["patches"], o["fine_pc"])) + (None, None)

@@ -626,20 +626,48 @@ def _kp_row_pos(feats, row_pos):
     return getattr(feats, "cofi_row_pos", None) if row_pos is None else row_pos
 
 
-def _kp_support(feats, s_pts, row_pos):
-    """Where the aggregation takes positions and positive-sum flags of the support from -> ("rec", records (N, 4)) or ("rows", row_pos):
-    the caller's or the attached row_pos, else records (attached or packed now), else - COFI_KPCONV_RECORDS=0 - row_sum_positive."""
+# Sorted index tables (the pyramid key "sorted_tables", INTEGRATION.md: valid entries first, in ascending canonical KNN distance, shadow
+# entries only behind them): the neighbours inside a kernel's support are a prefix of the row, and the aggregation gathers the records
+# of that prefix only (cofi_kpconv_aggregate_rec_sorted / _c4_sorted / cofi_kpconv_fused_rec_sorted); the positive-sum flags of all H
+# neighbours come from a bit table (kp_pack_bits).  Same bits as the unsorted kernels.  COFI_KPCONV_PREFIX=0: the unsorted kernels whatever
+# the caller promises (A/B runs, tests).
+def kpconv_prefix() -> bool:
+    return os.environ.get("COFI_KPCONV_PREFIX", "1") != "0"
+
+
+def kp_pack_bits(records: torch.Tensor, frames: int = 1) -> torch.Tensor:
+    """-> (frames, ceil(N / 32)) int32 words: bit n & 31 of word n >> 5 of a frame = the flag (last float) of the frame's record n.
+    records: (frames * N, 4) support records or (frames * N, 8) first-layer records."""
+    lib = _lib.load()
+    rows, stride = records.shape
+    if records.dtype != torch.float32 or not records.is_contiguous() or stride not in (4, 8) or rows == 0 or rows % frames:
+        raise _lib.CofiError("kp_pack_bits: records must be contiguous fp32 (frames * N, 4 or 8), N > 0")
+    N = rows // frames
+    bits = torch.empty((frames, int(lib.cofi_kp_bits_words(N))), dtype=torch.int32, device=records.device)
+    _lib.check(lib.cofi_kp_pack_bits(_p(records), stride, N, frames, _p(bits), _stream()), "cofi_kp_pack_bits")
+    return bits
+
+
+def _kp_support(feats, s_pts, row_pos, frames: int = 1, sorted_tables: bool = False):
+    """Where the aggregation takes positions and positive-sum flags of the support from -> ("rec", records (N, 4)), ("rows", row_pos) or
+    ("sorted", (records, flag bits)): the caller's or the attached row_pos, else records (attached or packed now; with the promise of
+    sorted index tables - and COFI_KPCONV_PREFIX not 0 - together with their flag bits), else - COFI_KPCONV_RECORDS=0 - row_sum_positive."""
     row_pos = _kp_row_pos(feats, row_pos)
     if row_pos is not None:
         return "rows", row_pos
     if kpconv_records():
-        return "rec", _support_records(feats, s_pts)
+        recs = _support_records(feats, s_pts)
+        if sorted_tables and kpconv_prefix() and recs.shape[0] > 0:
+            return "sorted", (recs, kp_pack_bits(recs, frames))
+        return "rec", recs
     return "rows", row_sum_positive(feats)
 
 
-def kpconv_aggregate(feats, q_pts, s_pts, idx, kernel_points, sigma: float, row_pos=None, frames: int = 1, order=None, planes: bool = False):
+def kpconv_aggregate(feats, q_pts, s_pts, idx, kernel_points, sigma: float, row_pos=None, frames: int = 1, order=None, planes: bool = False,
+                     sorted_tables: bool = False):
     """-> agg (M, 15*C), cnt (M,) float.  idx int32 (M,H).  Stack mode: `frames` equally sized frames stacked along
-    the rows of every argument, idx frame-local."""
+    the rows of every argument, idx frame-local.  sorted_tables: the caller's promise that the rows of idx are sorted (see
+    kpconv_prefix): same results from fewer gathers; on a table that breaks the promise the result is undefined."""
     lib = _lib.load()
     N, C, M, H = _kp_operands("kpconv_aggregate", feats, q_pts, s_pts, idx, kernel_points, frames)
     planes = planes and C % 4 == 0 and C > 4 and (15 * C) % 8 == 0
@@ -653,13 +681,19 @@ def kpconv_aggregate(feats, q_pts, s_pts, idx, kernel_points, sigma: float, row_
         # first layer: [features | position | positive-sum flag] packed into 32-byte records, one gather per neighbour
         recs = torch.empty((N, 8), dtype=torch.float32, device=feats.device)
         _lib.check(lib.cofi_kp_pack_c4(_p(feats), _ld(feats), C, _p(s_pts), N, _p(recs), _stream()), "cofi_kp_pack_c4")
-        rc = lib.cofi_kpconv_aggregate_c4(_p(recs), N // frames, C, _p(q_pts), *tail, _p(agg), 15 * C, _p(cnt), frames, _p(order), _stream())
-        _lib.check(rc, "cofi_kpconv_aggregate_c4")
+        out = (_p(agg), 15 * C, _p(cnt), frames, _p(order), _stream())
+        if sorted_tables and kpconv_prefix():
+            bits = kp_pack_bits(recs, frames)
+            _lib.check(lib.cofi_kpconv_aggregate_c4_sorted(_p(recs), _p(bits), N // frames, C, _p(q_pts), *tail, *out), "cofi_kpconv_aggregate_c4_sorted")
+        else:
+            _lib.check(lib.cofi_kpconv_aggregate_c4(_p(recs), N // frames, C, _p(q_pts), *tail, *out), "cofi_kpconv_aggregate_c4")
         return agg, cnt
     head = (_p(feats), _ld(feats), N // frames, C, _p(q_pts))
     out = (_p(agg), 15 * C, int(planes), _p(cnt), frames, _p(order), _stream())
-    kind, sup = _kp_support(feats, s_pts, row_pos)
-    if kind == "rec":
+    kind, sup = _kp_support(feats, s_pts, row_pos, frames, sorted_tables)
+    if kind == "sorted":
+        _lib.check(lib.cofi_kpconv_aggregate_rec_sorted(*head, _p(sup[0]), _p(sup[1]), *tail, *out), "cofi_kpconv_aggregate_rec_sorted")
+    elif kind == "rec":
         _lib.check(lib.cofi_kpconv_aggregate_rec(*head, _p(sup), *tail, *out), "cofi_kpconv_aggregate_rec")
     else:
         _lib.check(lib.cofi_kpconv_aggregate(*head, _p(s_pts), *tail, _p(sup), *out), "cofi_kpconv_aggregate")
@@ -674,9 +708,10 @@ def kpconv_fused_slab_rows(C: int, M: int, frames: int = 1) -> int:
 
 
 def kpconv_fused(feats, q_pts, s_pts, idx, kernel_points, sigma: float, w: "SplitW", bias, stat_width: int = 1, row_pos=None, frames: int = 1,
-                 order=None):
+                 order=None, sorted_tables: bool = False):
     """The whole KPConv operator (kpconv.py:91-116) of a narrow layer (C = 32 / 64 in = out channels) in one launch: -> (y (M, C),
-    statistics partials (M / slab_rows, C / stat_width, 2), slab_rows).  `w`: the (C, 15 C) packed weight as pre-split planes."""
+    statistics partials (M / slab_rows, C / stat_width, 2), slab_rows).  `w`: the (C, 15 C) packed weight as pre-split planes.
+    sorted_tables: as in kpconv_aggregate."""
     lib = _lib.load()
     N, C, M, H = _kp_operands("kpconv_fused", feats, q_pts, s_pts, idx, kernel_points, frames)
     if not isinstance(w, SplitW) or tuple(w.shape) != (C, 15 * C):
@@ -689,8 +724,10 @@ def kpconv_fused(feats, q_pts, s_pts, idx, kernel_points, sigma: float, w: "Spli
     head = (_p(feats), _ld(feats), N // frames, C, _p(q_pts))
     tail = (_p(idx), M // frames, H, _p(kernel_points), float(sigma))
     out = (_p(w.planes), w.ldp, _p(bias), _p(y), _ld(y), _p(part), stat_width, frames, _p(order), _stream())
-    kind, sup = _kp_support(feats, s_pts, row_pos)
-    if kind == "rec":
+    kind, sup = _kp_support(feats, s_pts, row_pos, frames, sorted_tables)
+    if kind == "sorted":
+        _lib.check(lib.cofi_kpconv_fused_rec_sorted(*head, _p(sup[0]), _p(sup[1]), *tail, *out), "cofi_kpconv_fused_rec_sorted")
+    elif kind == "rec":
         _lib.check(lib.cofi_kpconv_fused_rec(*head, _p(sup), *tail, *out), "cofi_kpconv_fused_rec")
     else:
         _lib.check(lib.cofi_kpconv_fused(*head, _p(s_pts), *tail, _p(sup), *out), "cofi_kpconv_fused")

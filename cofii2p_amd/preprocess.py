@@ -63,7 +63,11 @@ def build_pyramid(points: torch.Tensor, subsample: List[torch.Tensor], k: int = 
             "subsampling": [conv(t) for t in subsampling], "upsampling": [conv(t) for t in upsampling],
             # optional extra key: a spatially coherent processing order for the gather kernels (results do not depend on it) —
             # the cell order of the stage's grid where there is one; the few thousand points of the small stages stay as they are
-            "order": [g.order if g is not None else torch.arange(p.shape[0], dtype=torch.int32, device=p.device) for g, p in zip(grids, pts)]}
+            "order": [g.order if g is not None else torch.arange(p.shape[0], dtype=torch.int32, device=p.device) for g, p in zip(grids, pts)],
+            # optional extra key, a PROMISE: every row of neighbors[i] / subsampling[i] holds its valid entries first, in ascending canonical
+            # fp32 distance (csrc/knn_common.h; what ops.knn returns, and a row gather of it), shadow entries only behind them.  The KPConv
+            # aggregation then gathers the sorted prefix of a row only (ops.kpconv_prefix; results do not change by a bit)
+            "sorted_tables": True}
 
 
 class PyramidGraph:
@@ -123,14 +127,23 @@ class FrameStack:
         self.pyr = {k: [torch.empty((S * t.shape[0],) + tuple(t.shape[1:]), dtype=torch.float32 if k == "points" else torch.int32, device=dev)
                         for t in pyramid[k]] for k in self.KEYS}
         self.pyr["feats"] = torch.empty((S * feats.shape[0], feats.shape[1]), dtype=torch.float32, device=dev)
+        if pyramid.get("sorted_tables"):   # the promise of sorted neighbour rows: the stack makes it while its template and every frame put into it do
+            self.pyr["sorted_tables"] = True
         self.img = torch.empty((B,) + tuple(img.shape[-3:]), dtype=torch.float32, device=dev)
         self._mc = ops.MultiCopy(dev)
         self._mc.MAX_TABLES = 1 << 16   # one cached descriptor table per (producer slot, frame position): a few hundred bytes each
+
+    def _check_promise(self, pyramid: Dict):
+        """a frame that does not promise sorted neighbour rows takes the stack's promise away, for good: the next forward runs (and, under a
+        hipGraph, captures) the unsorted kernels"""
+        if not pyramid.get("sorted_tables"):
+            self.pyr.pop("sorted_tables", None)
 
     def put_cloud(self, s: int, pyramid: Dict, feats: torch.Tensor):
         """cloud s (0 <= s < B // cameras) <- the producer's tensors (int32 tables, contiguous), enqueued on the current stream"""
         if not 0 <= s < self.clouds:
             raise ValueError("cloud position %d outside the stack of %d" % (s, self.clouds))
+        self._check_promise(pyramid)
         srcs, dsts = [], []
         for k in self.KEYS:
             for t, d in zip(pyramid[k], self.pyr[k]):
@@ -154,6 +167,7 @@ class FrameStack:
             raise ValueError("FrameStack(cameras=%d): put() fills a (cloud, image) pair; use put_cloud and put_image" % self.cameras)
         if not 0 <= f < self.B:
             raise ValueError("frame position %d outside the stack of %d" % (f, self.B))
+        self._check_promise(pyramid)
         srcs, dsts = [], []
         for k in self.KEYS:
             for t, d in zip(pyramid[k], self.pyr[k]):

@@ -194,6 +194,21 @@ int cofi_kp_pack_support(const float *feats, int ldf, int N, int C, const float 
 int cofi_kpconv_aggregate_rec(const float *feats, int ldf, int N, int C, const float *q_pts, const float *records, const int32_t *idx,
                               int M, int H, const float *kernel_points, float sigma, float *agg, int ld_agg, int agg_planes, float *cnt,
                               int frames, const int32_t *order, cofi_stream_t stream);
+/* SORTED index tables.  Where the caller promises that in every row of idx the entries inside [0, N) come first, in ascending order of
+ * the canonical fp32 distance of the KNN kernels (cofi_knn: ((-2 q.s) + |q|^2) + |s|^2), and entries outside [0, N) only behind them,
+ * the neighbours inside the kernel's support are a prefix of the row: the _sorted entry points gather the records of that prefix only
+ * (neighbours 0 - 15, then 16 - 63, then 64 - 127, as far as something behind can still be inside) and take the positive-sum flags of
+ * all H neighbours from a bit table, (frames, cofi_kp_bits_words(N)) 32-bit words written by cofi_kp_pack_bits from the records
+ * (stride = floats per record: 4 for support records, 8 for the first layer's; the flag is the record's last float).  Same results as
+ * the unsorted entry points, bit for bit, on every table that keeps the promise; on any other table the result is undefined. */
+int cofi_kp_bits_words(int N);
+int cofi_kp_pack_bits(const float *records, int stride, int N, int frames, uint32_t *bits, cofi_stream_t stream);
+int cofi_kpconv_aggregate_rec_sorted(const float *feats, int ldf, int N, int C, const float *q_pts, const float *records, const uint32_t *bits,
+                                     const int32_t *idx, int M, int H, const float *kernel_points, float sigma, float *agg, int ld_agg,
+                                     int agg_planes, float *cnt, int frames, const int32_t *order, cofi_stream_t stream);
+int cofi_kpconv_aggregate_c4_sorted(const float *records, const uint32_t *bits, int N, int C, const float *q_pts, const int32_t *idx, int M, int H,
+                                    const float *kernel_points, float sigma, float *agg, int ld_agg, float *cnt, int frames,
+                                    const int32_t *order, cofi_stream_t stream);
 
 /* KPConv as ONE kernel for the narrow layers (C = 32 or 64 = in = out channels, the stages with the most queries):
  *   y[m] = (sum_k agg[m, k, :] W[k]) / max(#neighbours whose feature row sums to > 0, 1) + bias       (kpconv.py:91-116)
@@ -211,6 +226,11 @@ int cofi_kpconv_fused(const float *feats, int ldf, int N, int C, const float *q_
 int cofi_kpconv_fused_rec(const float *feats, int ldf, int N, int C, const float *q_pts, const float *records, const int32_t *idx, int M, int H,
                           const float *kernel_points, float sigma, const void *w_planes, int ldw, const float *bias, float *y, int ldy,
                           float *colpart, int stat_width, int frames, const int32_t *order, cofi_stream_t stream);
+/* cofi_kpconv_fused_rec for sorted index tables (see cofi_kpconv_aggregate_rec_sorted) */
+int cofi_kpconv_fused_rec_sorted(const float *feats, int ldf, int N, int C, const float *q_pts, const float *records, const uint32_t *bits,
+                                 const int32_t *idx, int M, int H, const float *kernel_points, float sigma, const void *w_planes, int ldw,
+                                 const float *bias, float *y, int ldy, float *colpart, int stat_width, int frames, const int32_t *order,
+                                 cofi_stream_t stream);
 /* K3 / K4  neighbour max-pool and nearest up-sample.
  * Replace model/kpconv/functional.py:53-66 (`maxpool`) and :5-21 (`nearest_upsample`): a zero
  * pad row stands behind index N. */

@@ -2,16 +2,21 @@
 """GPU tool: every KPConv aggregation launch of one stack-mode submission alone on the chip (hipGraph of 20 back-to-back replays, HIP
 events), on the neighbour tables of a synthetic pyramid and random features of each layer's width, in the form the forward uses
 (bf16 planes from 4 frames per submission, the stage's processing order); and, per layer, how many of the 128 neighbours of a query lie
-inside the kernel's support max|kp| + sigma (`nin`: mean / p95 / max, computed on the host from the tables).
+inside the kernel's support max|kp| + sigma (`nin`: mean / p95 / max, computed on the host from the tables), and the share of queries
+whose record gather reads 1 / 2 / 3 chunks (neighbours 0 - 15, 16 - 63, 64 - 127) in the sorted form - the fp32 emulation of the
+kernels' stop rule that the CPU test uses (tests/kpconv_prefix_ref.py), on frame 0's tables.
     python tools/kpconv_probe.py [frames=16] [points=20480]      -> a markdown table on stdout
-COFI_KPCONV_RECORDS=0 times the staging from separate position / flag arrays."""
+COFI_KPCONV_RECORDS=0 times the staging from separate position / flag arrays, COFI_KPCONV_PREFIX=0 the unsorted kernels (the launch
+that writes the flag bits of the sorted form is part of the layer's time)."""
 import os
 import sys
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
 import numpy as np
 import torch
 
+import kpconv_prefix_ref as prefix_ref
 from tools.gemm_shapes import time_graph
 
 
@@ -44,12 +49,13 @@ def main():
         pyrs.append(pyr)
     data = CoFiI2P.stack_frames(pyrs, [torch.zeros(1, 3, 8, 8, device=dev)] * frames)[0]
     pts, order = data["points"], data.get("order")
+    srt = bool(data.get("sorted_tables"))
     g = torch.Generator().manual_seed(1)
     records = ops.kpconv_records()
     planes = frames >= kpfpn.AGG_PLANES_MIN_FRAMES
-    print("| layer (%d frames of %d points, records %s) | kernel | queries | C | nin mean / p95 / max | real steps (mean) | us |"
-          % (frames, points, "on" if records else "off"))
-    print("|---|---|---|---|---|---|---|")
+    print("| layer (%d frames of %d points, records %s, sorted form %s) | kernel | queries | C | nin mean / p95 / max | real steps (mean) | "
+          "1 / 2 / 3 chunks | us |" % (frames, points, "on" if records else "off", "on" if srt and records and ops.kpconv_prefix() else "off"))
+    print("|---|---|---|---|---|---|---|---|")
     total = 0.0
     with torch.no_grad(), ops.arithmetic("bf16x6"):
         for blk in spec.ENCODER:
@@ -64,6 +70,12 @@ def main():
             sp = torch.cat([s[:Nf].cpu().double(), torch.full((1, 3), 1e9, dtype=torch.float64)], 0)
             d = (sp[i0.clamp(0, Nf)] - q[:Mf].cpu().double()[:, None]).norm(dim=2)
             nin = ((d < rsup) & (i0 < Nf)).sum(1).double()
+            # chunks of the sorted form's record gather, on the host
+            i0n = i0.numpy()
+            nvalid = (i0n < Nf).sum(1)
+            s0 = np.concatenate([s[:Nf].cpu().numpy(), np.zeros((1, 3), dtype=np.float32)])[np.clip(i0n, 0, Nf)]
+            ch = prefix_ref.chunks(q[:Mf].cpu().numpy(), s0, nvalid, prefix_ref.support_radius2(kp.cpu().numpy(), blk.sigma))
+            share = [float((ch == c).mean()) for c in (1, 2, 3)]
             feats = torch.randn(s.shape[0], C, generator=g).to(dev)
             o = None if order is None else order[st]
             pl = planes and C > 4
@@ -71,13 +83,14 @@ def main():
                 feats.cofi_kp_records = (ops.kp_pack_support(feats, s), s.data_ptr())
             elif C > 4:
                 feats.cofi_row_pos = ops.row_sum_positive(feats)
-            t = time_graph(lambda: ops.kpconv_aggregate(feats, q, s, idx, kp, blk.sigma, frames=frames, order=o, planes=pl))
+            t = time_graph(lambda: ops.kpconv_aggregate(feats, q, s, idx, kp, blk.sigma, frames=frames, order=o, planes=pl,
+                                                        sorted_tables=srt and C <= kpfpn.PREFIX_MAX_CHANNELS))   # as kpfpn.run_fpn routes it
             total += t
-            print("| %s | %s | %d | %d | %.1f / %.0f / %.0f | %.2f | %.1f |" % (blk.name, kernel_form(C), q.shape[0], C, float(nin.mean()),
-                                                                         float(nin.quantile(0.95)), float(nin.max()),
-                                                                         float(torch.ceil(nin / 4).mean()), t * 1e6))
+            print("| %s | %s | %d | %d | %.1f / %.0f / %.0f | %.2f | %.3f / %.3f / %.3f | %.1f |"
+                  % (blk.name, kernel_form(C), q.shape[0], C, float(nin.mean()), float(nin.quantile(0.95)), float(nin.max()),
+                     float(torch.ceil(nin / 4).mean()), share[0], share[1], share[2], t * 1e6))
             del feats
-    print("| **all 14 layers** | | | | | | **%.1f** |" % (total * 1e6))
+    print("| **all 14 layers** | | | | | | | **%.1f** |" % (total * 1e6))
 
 
 if __name__ == "__main__":
