@@ -168,6 +168,8 @@ SIGNATURES = {
     "cofi_gather_transform": (_I, [_P, _P, _I, _P, _P, _P, _I, _P]),
     "cofi_resize_crop_image": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
     "cofi_estimate_normals": (_I, [_P, _I, _P, _P, _I, _I, _I, _F, _P, _P, ctypes.c_longlong, ctypes.c_longlong, _P, _P]),
+    "cofi_fuse_workspace": (_Z, [_I, _I, _I]),
+    "cofi_fuse_cloud_image": (_I, [_P, _I, _I, _I, _P, _I, _I, _I, _P, _I, _P, _I, _P, _F, _F, _I, _F, _F, _P, _Z, _P, _P, _P, _P, _P, _P, _P]),
 }
 
 

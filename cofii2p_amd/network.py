@@ -496,7 +496,7 @@ class CoFiI2P(nn.Module):
 
     @torch.no_grad()
     def forward_async(self, slot: int, pc_data_dict, img, mode: str = "test", inputs_stable: bool = False, pose_K=None,
-                      pose_iterations: int = 10000, pose_seed: int = 0, eval_into=None, cameras: int = 1, rig_extrinsics=None):
+                      pose_iterations: int = 10000, pose_seed: int = 0, eval_into=None, cameras: int = 1, rig_extrinsics=None, fuse_into=None):
         """Enqueue one test-mode forward on the CURRENT stream through the hipGraph of slot `slot` and return
         immediately (no host sync).  `img` (1,3,H,W) = one frame, or (B,3,H,W) with a stack-mode `pc_data_dict`
         (see stack_frames) = B frames through the same launches.  Slots own their static buffers and scratch, so
@@ -536,7 +536,15 @@ class CoFiI2P(nn.Module):
         four per-image entries - now E_c o rig pose, this image's inliers of the rig's consensus, its mask - so eval_into and every other
         reader of per-image poses work unchanged, and the handle gains handle["rig_pose"] = {"result" (S,3) int32 [success, inliers over
         all cameras, hypothesis], "R" (S,3,3), "t" (S,3)}.  Refused before anything is enqueued: rig_extrinsics without pose_K or with
-        cameras == 1."""
+        cameras == 1.
+
+        fuse_into=buffers (a fusion.FusionBuffers; needs pose_K): the registered cloud of the submission (fusion.fuse_into: depth and
+        point-id maps per image, in-picture / visible flags, one colour and camera per point) is enqueued behind the pose tail - the rig
+        pose tail with rig_extrinsics - on the same stream, before the handle's `done` event.  It reads the submission's finest points
+        (`points[0]`: S = B // cameras clouds of N rows), its images, the per-image poses and results of handle["pose"], and pose_K with
+        k_scale = image width / fine-map width (pose_K belongs to the fine map the matches live on).  handle["fusion"] = buffers.  Refused
+        before anything is enqueued: fuse_into without pose_K, buffers that were not made for (S, N, B, H, W, 3) on the device of the
+        images.  With the default None nothing about the call, its handle or its launches changes."""
         if mode != "test":
             if cameras != 1:
                 raise ValueError("a rig (cameras = %d > 1) serves mode='test' only, got mode=%r" % (cameras, mode))
@@ -563,9 +571,20 @@ class CoFiI2P(nn.Module):
             if pose_K is None:
                 raise _lib.CofiError("forward_async(eval_into=...): the monitors read the submission's poses - pass pose_K")
             evaluation.check_eval_into(eval_into, img.shape[0] if img.dim() == 4 else 1, img.device)
+        if fuse_into is not None:
+            from . import fusion
+
+            if pose_K is None:
+                raise _lib.CofiError("forward_async(fuse_into=...): the fusion reads the submission's poses - pass pose_K")
+            B = img.shape[0] if img.dim() == 4 else 1
+            S, rows = B // cameras, pc_data_dict["points"][0].shape[0]
+            want = (S, rows // S, B, img.shape[-2], img.shape[-1], img.shape[-3])
+            if not isinstance(fuse_into, fusion.FusionBuffers) or rows % S or not fuse_into.fits(*want, img.device):
+                raise _lib.CofiError("forward_async(fuse_into=...): need a fusion.FusionBuffers made for (S, N, F, H, W, Ci) = %s on %s"
+                                     % (want, img.device))
         with ops.arithmetic(self.arithmetic):
             return self._forward_async(slot, pc_data_dict, img, mode, inputs_stable, pose_K, pose_iterations, pose_seed, eval_into, cameras,
-                                       rig_extrinsics)
+                                       rig_extrinsics, fuse_into)
 
     @staticmethod
     def _check_rig(pc_data_dict, img, cameras):
@@ -633,7 +652,7 @@ class CoFiI2P(nn.Module):
         return {"result": res, "R": R, "t": t, "inliers": mask}, K, None
 
     def _forward_async(self, slot, pc_data_dict, img, mode, inputs_stable, pose_K=None, pose_iterations=10000, pose_seed=0, eval_into=None,
-                       cameras=1, rig_ext=None):
+                       cameras=1, rig_ext=None, fuse_into=None):
         P = self._pack(img.device)
         if inputs_stable:
             for k in ("points", "neighbors", "subsampling", "upsampling"):
@@ -661,9 +680,17 @@ class CoFiI2P(nn.Module):
             from . import evaluation
 
             evaluation.eval_monitors({"out": outs, "pose": pose}, K_dev, eval_into[1], eval_into[0], eval_into[2])
+        if fuse_into is not None:   # the registered cloud of the submission: four launches behind the pose tail
+            from . import fusion
+
+            im = img.contiguous().reshape((-1,) + tuple(img.shape[-3:]))
+            fusion.fuse_into(points[0], im, pose, K_dev, fuse_into, result=pose["result"], cameras=cameras,
+                             k_scale=float(im.shape[3]) / float(4 * (im.shape[3] // 8)))
         done = torch.cuda.Event()
         done.record()
         handle = {"out": outs, "count_host": host, "done": done}
+        if fuse_into is not None:
+            handle["fusion"] = fuse_into
         if pose is not None:
             handle["pose"] = pose
         if rig_pose is not None:

@@ -36,6 +36,11 @@ Rig pose (the C cameras are bolted to one body: ONE pose per rig from the matche
 for every rig, or `rig_extrinsics="per_rig"` and `submit_rig(..., extrinsics=E)` with each rig's own (C,4,4) / (C,3,4).
 `rig_pose_result(t)` -> (result (3,) int32 [success, inliers over all cameras, hypothesis], R (3,3), t (3,)) of the ticket's rig, rig <-
 cloud; `pose_result(t)` stays per image and holds E_c o rig pose with that image's share of the consensus.
+
+Registered clouds (`fusion.fuse_into` behind the pose tail of every stack): `FrameBatcher(model, pose=True, fuse=True[, cameras=C,
+rig_extrinsics=E])`; `fusion_result(t)` -> {"depth" (H,W), "index" (H,W), "flags" (N,), "stats" (4,)} of the ticket's image plus "color"
+(N,3) and "camera" (N,) of its cloud - with cameras = C the maps of all C images of the ticket's rig, (C,H,W) / (C,N) / (C,4).  One
+`fusion.FusionBuffers` per stack of the ring, so the views live as long as `result(t)` does.
 """
 from typing import Dict, List, Optional, Tuple
 
@@ -47,9 +52,12 @@ from .preprocess import FrameStack
 
 class FrameBatcher:
     def __init__(self, model: CoFiI2P, batch: int = 16, streams: int = 4, ring: Optional[int] = None, slot_base: int = 200,
-                 pose: bool = False, pose_iterations: int = 10000, eval_table=None, cameras: int = 1, rig_extrinsics=None):
+                 pose: bool = False, pose_iterations: int = 10000, eval_table=None, cameras: int = 1, rig_extrinsics=None,
+                 fuse: bool = False):
         if batch < 1:
             raise ValueError("batch must be >= 1")
+        if fuse and not pose:
+            raise ValueError("FrameBatcher(fuse=True): the fusion reads the poses - pass pose=True")
         if cameras < 1 or batch % cameras:
             raise ValueError("batch = %d is no whole number of rigs of cameras = %d" % (batch, cameras))
         self.model, self.B, self.C = model, int(batch), int(cameras)
@@ -93,6 +101,8 @@ class FrameBatcher:
         self._ext_shared = None if self.rig_per_rig else rig_extrinsics
         self._ext: List[Optional[torch.Tensor]] = [None] * self.ring  # (S,C,12) device buffer of each stack (per-rig extrinsics)
         self._rig_poses: List[Optional[Dict]] = [None] * self.ring    # handle["rig_pose"] of the stack's finished submission
+        self.fuse = bool(fuse)
+        self._fusion: List[Optional[object]] = [None] * self.ring     # the stack's fusion.FusionBuffers, made at its first submission
 
     # ------------------------------------------------------------------ internals
     def _stream(self, j: int) -> torch.cuda.Stream:
@@ -122,6 +132,14 @@ class FrameBatcher:
         rig = {} if self.C == 1 else {"cameras": self.C}
         if self.rig:
             rig["rig_extrinsics"] = self._rig_ext(j)
+        if self.fuse:
+            if self._fusion[j] is None:
+                from . import fusion
+
+                clouds = self.B // self.C
+                self._fusion[j] = fusion.FusionBuffers(clouds, st.pyr["points"][0].shape[0] // clouds, self.B, st.img.shape[2], st.img.shape[3],
+                                                       st.img.shape[1], st.img.device)
+            rig["fuse_into"] = self._fusion[j]
         with torch.cuda.stream(self._stream(j)):
             if self.eval_table is not None:
                 self._handles[j] = self.model.forward_async(self.slot_base + j, st.pyr, st.img, inputs_stable=True, pose_K=self._K[j],
@@ -352,6 +370,20 @@ class FrameBatcher:
         r = self._rig_poses[ticket[0]]
         s = ticket[2] // self.C
         return r["result"][s], r["R"][s], r["t"][s]
+
+    def fusion_result(self, ticket: Tuple[int, int, int]) -> Dict[str, torch.Tensor]:
+        """-> the registered cloud of the ticket's frame: {"depth" (H,W) float32, "index" (H,W) int32, "flags" (N,) uint8, "stats" (4,) int32}
+        of its image, "color" (N,3) and "camera" (N,) int32 of its cloud (fusion.FusionBuffers has the meanings).  With cameras = C the
+        four per-image entries hold all C images of the ticket's rig - (C,H,W), (C,H,W), (C,N), (C,4) - the same for its C tickets.
+        Device views of the stack's buffers, same lifetime as `result(ticket)`."""
+        if not self.fuse:
+            raise RuntimeError("FrameBatcher: built without fuse=True")
+        self.pose_result(ticket)   # the ticket checks, the flush and the collection
+        b, f, C = self._fusion[ticket[0]], ticket[2], self.C
+        s = f // C
+        img = slice(s * C, (s + 1) * C) if C > 1 else f
+        return {"depth": b.depth[img], "index": b.index[img], "flags": b.flags[img], "stats": b.stats[img], "color": b.color[s],
+                "camera": b.camera[s]}
 
     @property
     def submissions(self) -> int:

@@ -816,6 +816,42 @@ int cofi_estimate_normals(const float *points, int S, const int32_t *idx, const 
                           const float *viewpoint3_dev, float *out, long long out_point_stride, long long out_comp_stride,
                           int32_t *degenerate_count_dev, cofi_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Registered clouds: the `images` = F = S * C images of a submission joined with its S = F / cameras clouds through the per-image poses
+ * of the pose tail - z-buffered depth and point-id maps per image, in-picture / visible flags per (image, point), and per point the
+ * colour of the camera that sees it most centrally.  The reference has offline numpy helpers only (data/kitti_helper.py:166-190
+ * crop_pc_with_img, :142-163 projection_pc_img), without occlusion; the contract is this project's.  Operands are read in place:
+ *   points  (S * N, 3), cloud s at rows s * N ...; image f looks at cloud f / cameras
+ *   img     (F, Ci, H, W) float32
+ *   pose    image f at pose + f * pose_stride floats (pose_stride >= 12): [R row-major | t], camera <- cloud, as cofi_pnp_ransac_batch /
+ *           cofi_pnp_ransac_rig write their per-image poses
+ *   result  optional (NULL: every image takes part): image f contributes nothing when result[f * result_stride] == 0
+ *   K_dev   (F, 3, 3) float32 in DEVICE memory; fx, fy, cx, cy are each multiplied by k_scale (one fp32 product; the convention of
+ *           camera_matrix_scaling, data/kitti.py:188-191: a half-resolution K serves the full image with k_scale = 2)
+ * Projection (fp32, one device function for every pass, each operation a correctly rounded fma / division, no contraction): camera
+ * coordinates by rows, fma(r2, Z, fma(r1, Y, fma(r0, X, t))); u = fma(fx, x / z, cx), v = fma(fy, y / z, cy); pixel = rintf (ties to even, as
+ * np.round); in picture = z > z_near and 0 <= px <= W - 1 and 0 <= py <= H - 1, compared as floats so that a NaN is out.
+ *   pass 1  every in-picture point: atomicMin of the key (float bits of z) << 32 | cloud-local point id on the (2 splat + 1)^2 pixels around
+ *           its own, clipped to the image: the nearest point wins a pixel, the lowest id among equal depths, in any order of arrival
+ *   pass 2  visible in a camera = in picture and z <= zmin * (1 + rel_tol) + abs_tol (one fma), zmin decoded from the key of its own pixel.
+ *           Among the cameras that see a point the one with the smallest ((u - cx) / fx)^2 + ((v - cy) / fy)^2 gives the colour (lowest
+ *           camera on ties): bilinear at (u, v), pixel centres at integer coordinates, the four taps clamped to the edge, weights
+ *           (1-ax)(1-ay), ax(1-ay), (1-ax)ay, ax ay and the sum fma(w11, p11, fma(w10, p10, fma(w01, p01, w00 p00))).
+ *   pass 3  keys -> maps
+ * Outputs: depth (F, H, W) float32, 0 where empty; index (F, H, W) int32 cloud-local id, -1 where empty; flags (F, N) uint8, bit 0 in
+ * picture, bit 1 visible; color (S, N, Ci) float32, 0 where unseen; camera (S, N) int32, -1 where unseen; stats (F, 4) int32 = {in
+ * picture, visible, pixels hit, 0} (zeroed here; counted per workgroup, then one integer atomic each).  With splat > 0 a point can own a
+ * neighbouring pixel while failing the gate at its own, so `index` may hold ids that are in picture but not visible; with splat 0 every id
+ * in `index` is visible.  ws: cofi_fuse_workspace(F, H, W) = 8 bytes per pixel (0 for non-positive arguments or F * H * W beyond 31
+ * bits), 8-byte aligned.  COFI_EINVAL: a NULL required pointer, non-positive sizes, cameras not dividing images, splat outside 0..3,
+ * z_near or k_scale not positive, a negative tolerance, F * H * W beyond 31 bits; COFI_EWORKSPACE: ws too small; COFI_EUNSUPPORTED:
+ * images > 65535.  Four launches on `stream` (the first clears the keys to the all-ones sentinel and the stats), no host synchronisation. */
+size_t cofi_fuse_workspace(int images, int H, int W);
+int cofi_fuse_cloud_image(const float *points, int N, int images, int cameras, const float *img, int Ci, int H, int W, const float *pose,
+                          int pose_stride, const int32_t *result, int result_stride, const float *K_dev, float k_scale, float z_near,
+                          int splat, float rel_tol, float abs_tol, void *ws, size_t ws_bytes, float *depth, int32_t *index, uint8_t *flags,
+                          float *color, int32_t *camera, int32_t *stats, cofi_stream_t stream);
+
 /* Batched device-to-device copy in one launch: descs_dev = n records {const void *src; void *dst; uint64 bytes} in device
  * memory (e.g. the per-frame inputs -> the static buffers of a captured forward graph); blocks_per_copy workgroups per record. */
 int cofi_multi_copy(const void *descs_dev, int n, int blocks_per_copy, cofi_stream_t stream);
