@@ -66,6 +66,8 @@ SIGNATURES = {
     "cofi_kpconv_aggregate_rec_sorted": (_I, [_P, _I, _I, _I, _P, _P, _P, _P, _I, _I, _P, _F, _P, _I, _I, _P, _I, _P, _P]),
     "cofi_kpconv_aggregate_c4_sorted": (_I, [_P, _P, _I, _I, _P, _P, _I, _I, _P, _F, _P, _I, _P, _I, _P, _P]),
     "cofi_neighbor_maxpool": (_I, [_P, _I, _I, _I, _P, _I, _I, _P, _I, _I, _P, _P]),
+    "cofi_neighbor_maxpool_slice_ok": (_I, [_I, _I, _I, _I]),
+    "cofi_neighbor_maxpool_slice": (_I, [_P, _I, _I, _I, _P, _I, _I, _P, _I, _I, _P, _P]),
     "cofi_gather_rows": (_I, [_P, _I, _I, _I, _P, _I, _I, _P, _I, _I, _P]),
     "cofi_gemm_f16x3_eligible": (_I, [_I, _I, _I, _I, _I]),
     "cofi_conv2d_f16x3_eligible": (_I, [_I, _I, _I, _I, _I, _I, _I, _I, _I, _I]),
@@ -224,7 +226,10 @@ def load():
     return lib
 
 
+COFI_EINVAL, COFI_EWORKSPACE, COFI_EUNSUPPORTED = -1, -2, -3   # include/cofi_hip.h
+
+
 def check(rc: int, what: str):
     if rc != 0:
-        kind = {-1: "COFI_EINVAL", -2: "COFI_EWORKSPACE", -3: "COFI_EUNSUPPORTED"}.get(rc, "hipError %d" % rc)
+        kind = {COFI_EINVAL: "COFI_EINVAL", COFI_EWORKSPACE: "COFI_EWORKSPACE", COFI_EUNSUPPORTED: "COFI_EUNSUPPORTED"}.get(rc, "hipError %d" % rc)
         raise CofiError("%s failed: %s" % (what, kind))

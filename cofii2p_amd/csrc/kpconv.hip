@@ -892,6 +892,157 @@ __global__ __launch_bounds__(256) void neighbor_maxpool_kernel(const float *x, i
     if (g == 0 && cin) *reinterpret_cast<float4 *>(out + (size_t)m * ldo + c) = best;
 }
 
+// The same max-pool for a source that fits one CU's LDS a few channels at a time (deep stages: few rows, many channels, every source
+// row listed by ~64 queries).  One 16-wave workgroup owns (frame, group of CH channels, one of S query ranges): it loads the frame's
+// N x CH slice ONCE, coalesced - no union of neighbour lists to find - behind it a zero row (N: every index outside [0, N)) and a -inf
+// row (N + 1: positions past the end of an index row), and then serves all H neighbours of its queries from LDS.
+//   lanes     CH / 4 lanes per query, each folds one float4 of channels over all H neighbours: no cross-lane reduction.
+//   staging   per wave and pass, the index rows of its 64 / (CH / 4) queries, HC neighbours at a time, as BYTE OFFSETS into the slice
+//             (range rule applied once per index, not once per channel quad); a wave reads what it wrote itself: no block barrier in
+//             the loop.  A query's HC offsets are HC / 4 16-byte quads, quad k stored at k ^ swz(query), so that the 16 lanes that a
+//             ds_read_b128 serves together (MI355X: lanes {0-3, 12-15, 20-27}, ...) read 16 different bank quads.
+//   the fold  fmaxf from -inf in neighbour order: the maximum is exact in any order, so the bits are neighbor_maxpool_kernel's.
+// `order` plays no part: a workgroup walks all queries of its range whatever their order.
+constexpr int MPS_WAVES = 16, MPS_STAGE = 1024;   // waves per workgroup; staged offsets per wave (4 KB)
+
+template <int CH, int ROWS>
+__global__ __launch_bounds__(64 * MPS_WAVES) void neighbor_maxpool_slice_kernel(const float *x, int ldx, int N, int C, const int32_t *idx, int Mpf,
+                                                                                int H, float *out, int ldo, int S, int G, int vec) {
+    constexpr int LPQ = CH / 4;          // lanes per query
+    constexpr int QW = 64 / LPQ;         // queries per wave and pass
+    constexpr int HC = MPS_STAGE / QW;   // neighbours per staged chunk
+    constexpr int HQ = HC / 4;           // 16-byte quads per staged index row
+    __shared__ float4 slice[ROWS * LPQ];
+    __shared__ int4 stage[MPS_WAVES][MPS_STAGE / 4];
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int b = xcd_contiguous_block(blockIdx.x, gridDim.x);   // the channel groups of a frame share lines of x and the index table: one XCD
+    const int g = b % G, s = (b / G) % S, f = b / (G * S);
+    const int c0 = g * CH;
+    x += (size_t)f * N * ldx;
+    idx += (size_t)f * Mpf * H;
+    out += (size_t)f * Mpf * ldo;
+    {   // the slice: rows 0 .. N-1, then the zero row and the -inf row
+        const int quad = tid % LPQ, c = c0 + quad * 4;
+        constexpr int RSTEP = 64 * MPS_WAVES / LPQ;
+        if ((vec & 1) && c0 + CH <= C) {
+#pragma unroll 4
+            for (int r = tid / LPQ; r < N; r += RSTEP) slice[r * LPQ + quad] = *reinterpret_cast<const float4 *>(x + (size_t)r * ldx + c);
+        } else {
+            for (int r = tid / LPQ; r < N; r += RSTEP) {
+                const float *p = x + (size_t)r * ldx;
+                slice[r * LPQ + quad] = make_float4(c < C ? p[c] : 0.f, c + 1 < C ? p[c + 1] : 0.f, c + 2 < C ? p[c + 2] : 0.f, c + 3 < C ? p[c + 3] : 0.f);
+            }
+        }
+        if (tid < 2 * LPQ) {
+            const float v = tid < LPQ ? 0.f : -INFINITY;
+            slice[N * LPQ + tid] = make_float4(v, v, v, v);
+        }
+    }
+    __syncthreads();
+    const int per = (Mpf + S - 1) / S, lo = s * per, hi = min(Mpf, lo + per);
+    const int ql = lane / LPQ, quad = lane % LPQ, c = c0 + quad * 4;
+    const int swz = (ql / (64 / HC)) & (HQ - 1);
+    const char *sbase = reinterpret_cast<const char *>(slice) + quad * 16;
+    int4 *st = stage[wv];
+    // one chunk = HC neighbours of the pass's QW queries; the index loads of the next chunk are in flight while this one is folded
+    // -> whether the chunk is FULL (wave-uniform): every query of the pass exists, every neighbour of the chunk too, 16-byte index loads -
+    // four unconditional loads per lane now and no range tests on h when the offsets are written
+    const int lane_off = (lane / HQ) * H + (lane % HQ) * 4;
+    auto load = [&](int q0, int h0, int4 (&o)[4]) -> bool {   // 4 quads per lane, consecutive lanes on consecutive quads of an index row
+        const bool full = (vec & 4) && h0 + HC <= H && q0 + QW <= hi;
+        if (full) {
+            const int32_t *p = idx + ((size_t)q0 * H + h0) + lane_off;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) o[i] = *reinterpret_cast<const int4 *>(p + (size_t)(i * (64 / HQ)) * H);
+            return true;
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int e = i * 64 + lane, qs = e / HQ, h = h0 + (e % HQ) * 4;
+            const bool live = q0 + qs < hi;   // a query past the range reads nothing (its lanes fold the zero row and store nothing)
+            const int32_t *p = idx + (size_t)(q0 + qs) * H + h;
+            o[i].x = live && h < H ? p[0] : -1;
+            o[i].y = live && h + 1 < H ? p[1] : -1;
+            o[i].z = live && h + 2 < H ? p[2] : -1;
+            o[i].w = live && h + 3 < H ? p[3] : -1;
+        }
+        return false;
+    };
+    int4 o[4];
+    int q0 = lo + wv * QW, h0 = 0;
+    bool full = q0 < hi && load(q0, 0, o);
+    float4 best = make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY);
+    while (q0 < hi) {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");   // the previous chunk's reads are done before its offsets are replaced
+        __builtin_amdgcn_wave_barrier();
+        // anything outside [0, N) -> the zero row N; past the end of the index row -> the -inf row N + 1
+        if (full) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int qs = (i * 64 + lane) / HQ, k = lane % HQ;
+                st[qs * HQ + (k ^ ((qs / (64 / HC)) & (HQ - 1)))] =
+                    make_int4((int)min((unsigned)o[i].x, (unsigned)N) * (CH * 4), (int)min((unsigned)o[i].y, (unsigned)N) * (CH * 4),
+                              (int)min((unsigned)o[i].z, (unsigned)N) * (CH * 4), (int)min((unsigned)o[i].w, (unsigned)N) * (CH * 4));
+            }
+        } else {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int e = i * 64 + lane, qs = e / HQ, k = e % HQ, h = h0 + k * 4;
+                int4 r;
+                r.x = h < H ? (int)min((unsigned)o[i].x, (unsigned)N) : N + 1;
+                r.y = h + 1 < H ? (int)min((unsigned)o[i].y, (unsigned)N) : N + 1;
+                r.z = h + 2 < H ? (int)min((unsigned)o[i].z, (unsigned)N) : N + 1;
+                r.w = h + 3 < H ? (int)min((unsigned)o[i].w, (unsigned)N) : N + 1;
+                st[qs * HQ + (k ^ ((qs / (64 / HC)) & (HQ - 1)))] = make_int4(r.x * (CH * 4), r.y * (CH * 4), r.z * (CH * 4), r.w * (CH * 4));
+            }
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        int nq0 = q0, nh0 = h0 + HC;
+        if (nh0 >= H) {
+            nh0 = 0;
+            nq0 += MPS_WAVES * QW;
+        }
+        full = nq0 < hi && load(nq0, nh0, o);
+        const int nq = (min(HC, H - h0) + 3) >> 2;
+        auto fold = [&](const int4 a) {
+            const float4 v0 = *reinterpret_cast<const float4 *>(sbase + a.x), v1 = *reinterpret_cast<const float4 *>(sbase + a.y);
+            const float4 v2 = *reinterpret_cast<const float4 *>(sbase + a.z), v3 = *reinterpret_cast<const float4 *>(sbase + a.w);
+            best.x = fmaxf(fmaxf(best.x, v0.x), fmaxf(fmaxf(v1.x, v2.x), v3.x));
+            best.y = fmaxf(fmaxf(best.y, v0.y), fmaxf(fmaxf(v1.y, v2.y), v3.y));
+            best.z = fmaxf(fmaxf(best.z, v0.z), fmaxf(fmaxf(v1.z, v2.z), v3.z));
+            best.w = fmaxf(fmaxf(best.w, v0.w), fmaxf(fmaxf(v1.w, v2.w), v3.w));
+        };
+        if (nq == HQ) {   // a full chunk: all offset quads first, then the row reads back to back - the waits are counted, not drained
+            int4 a[HQ];
+#pragma unroll
+            for (int k = 0; k < HQ; ++k) a[k] = st[ql * HQ + (k ^ swz)];
+#pragma unroll
+            for (int k = 0; k < HQ; ++k) fold(a[k]);
+        } else {
+            for (int k = 0; k < nq; ++k) fold(st[ql * HQ + (k ^ swz)]);
+        }
+        if (nh0 == 0) {   // the pass's last chunk
+            const int m = q0 + ql;
+            if (m < hi) {
+                float *po = out + (size_t)m * ldo;
+                if ((vec & 2) && c + 4 <= C) {
+                    *reinterpret_cast<float4 *>(po + c) = best;
+                } else {
+                    if (c < C) po[c] = best.x;
+                    if (c + 1 < C) po[c + 1] = best.y;
+                    if (c + 2 < C) po[c + 2] = best.z;
+                    if (c + 3 < C) po[c + 3] = best.w;
+                }
+            }
+            best = make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY);
+        }
+        q0 = nq0;
+        h0 = nh0;
+    }
+}
+
 // out[m,:] = x[idx[m*idx_stride], :] (zero row for idx == N)
 __global__ void gather_rows_kernel(const float *x, int ldx, int N, int C, const int32_t *idx, int idx_stride, int M, float *out,
                                    int ldo, int Mpf) {
@@ -1134,6 +1285,37 @@ extern "C" int cofi_neighbor_maxpool(const float *x, int ldx, int N, int C, cons
     if (frames <= 0) return COFI_EINVAL;
     hipLaunchKernelGGL(neighbor_maxpool_kernel, dim3(cofi_cdiv(M * frames, 4), cofi_cdiv(C, 32)), dim3(256), 0, cofi_s(stream), x, ldx, N,
                        C, idx, M * frames, H, out, ldo, M, order);
+    return cofi_launch_status();
+}
+
+// The slice form: N source rows + the zero row + the -inf row at 8 channels (3072 rows) or 4 channels (6144 rows) of fp32 in 96 KB, next to
+// the 64 KB of staged offsets.  0: the slice does not fit at 4 channels.
+constexpr int MPS_ROWS8 = 3072, MPS_ROWS4 = 6144;
+static int mps_channels(int N, int C) { return N + 2 <= MPS_ROWS8 && C > 4 ? 8 : (N + 2 <= MPS_ROWS4 ? 4 : 0); }
+
+extern "C" int cofi_neighbor_maxpool_slice_ok(int N, int C, int H, int frames) {
+    return N > 0 && C > 0 && H > 0 && frames > 0 && mps_channels(N, C) != 0;
+}
+
+extern "C" int cofi_neighbor_maxpool_slice(const float *x, int ldx, int N, int C, const int32_t *idx, int M, int H, float *out, int ldo,
+                                           int frames, const int32_t *order, cofi_stream_t stream) {
+    (void)order;   // a workgroup serves every query of its range from one slice: the processing order plays no part
+    if (!x || !idx || !out || N <= 0 || C <= 0 || M < 0 || H <= 0 || ldx < C || ldo < C || frames <= 0) return COFI_EINVAL;
+    const int ch = mps_channels(N, C);
+    if (ch == 0) return COFI_EUNSUPPORTED;
+    if (M == 0) return 0;
+    const int G = cofi_cdiv(C, ch), passes = cofi_cdiv(M, MPS_WAVES * (256 / ch));
+    if ((long)frames * G * passes >= (1L << 31)) return COFI_EUNSUPPORTED;
+    // few frames: split a frame's queries over S workgroups per channel group, down to one pass per wave, until the chip is covered twice
+    const int S = std::max(1, std::min(passes, 512 / (frames * G)));
+    const int vec = ((ldx & 3) == 0 && ((uintptr_t)x & 15) == 0 ? 1 : 0) | ((ldo & 3) == 0 && ((uintptr_t)out & 15) == 0 ? 2 : 0) |
+                    ((H & 3) == 0 && ((uintptr_t)idx & 15) == 0 ? 4 : 0);
+    if (ch == 8)
+        hipLaunchKernelGGL((neighbor_maxpool_slice_kernel<8, MPS_ROWS8>), dim3(frames * G * S), dim3(64 * MPS_WAVES), 0, cofi_s(stream), x, ldx, N, C,
+                           idx, M, H, out, ldo, S, G, vec);
+    else
+        hipLaunchKernelGGL((neighbor_maxpool_slice_kernel<4, MPS_ROWS4>), dim3(frames * G * S), dim3(64 * MPS_WAVES), 0, cofi_s(stream), x, ldx, N, C,
+                           idx, M, H, out, ldo, S, G, vec);
     return cofi_launch_status();
 }
 

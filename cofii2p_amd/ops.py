@@ -734,6 +734,42 @@ def kpconv_fused(feats, q_pts, s_pts, idx, kernel_points, sigma: float, w: "Spli
     return y, part, sr
 
 
+# The slice form of the neighbour max-pool (cofi_neighbor_maxpool_slice): a workgroup keeps a frame's source, 8 or 4
+# channels wide, in LDS and serves every neighbour of the frame's queries from there.  Same bits as the gather kernel.  Measured on MI355X
+# (profiles/maxpool_slice/README.md), us per launch at batch 16, gather -> slice, alone on the chip / in the pipeline's kernel trace:
+#   encoder5_1 (2 560 rows per frame, 8 channels per group)   408 - 432 -> 268 - 276  /  458 - 461 -> 293
+#   encoder4_1 (5 120 rows per frame, 4 channels per group)   439 - 471 -> 353 - 360  /  477 - 479 -> 388
+#   encoder3_1 (10 240 rows) does not fit at 4 channels; at 2 the index table would be re-read 128 times.
+# MAXPOOL_SLICE_MAX_ROWS is that limit.  Routed in stack mode only, from MAXPOOL_SLICE_MIN_FRAMES frames per submission (at 4 frames the
+# probe gives 113 -> 95 and 114 -> 75 us and bench.py --batch 4 is not slower, 736 -> 744 frames/s by the medians inside the parent's
+# spread - a threshold set at "not slower"; at 8 frames 216 -> 177 and 218 -> 139 us, --batch 8 849 -> 868 with every new run above every
+# parent run): a single frame would put a few hundred workgroups of 160 KB on the chip, each holding a whole CU against the kernels of the other
+# submissions in flight.  COFI_MAXPOOL_SLICE=0: the gather kernel everywhere (A/B runs, tests).
+MAXPOOL_SLICE_MIN_FRAMES = 4
+MAXPOOL_SLICE_MAX_ROWS = 5120
+
+
+def maxpool_slice() -> bool:
+    return os.environ.get("COFI_MAXPOOL_SLICE", "1") != "0"
+
+
+def neighbor_maxpool_slice_ok(N: int, C: int, H: int, frames: int = 1) -> bool:
+    """Whether cofi_neighbor_maxpool_slice serves N source rows per frame (the slice fits the LDS of a CU)."""
+    return bool(_lib.load().cofi_neighbor_maxpool_slice_ok(N, C, H, frames))
+
+
+def neighbor_maxpool_slice(x, idx, out=None, frames: int = 1, order=None):
+    """neighbor_maxpool on the slice kernel, whatever the routing says; COFI_EUNSUPPORTED where the slice does not fit."""
+    lib = _lib.load()
+    _mat(x, "x"), _mat(idx, "idx", torch.int32)
+    M, H = idx.shape
+    if out is None:
+        out = torch.empty((M, x.shape[1]), dtype=torch.float32, device=x.device)
+    _lib.check(lib.cofi_neighbor_maxpool_slice(_p(x), _ld(x), x.shape[0] // frames, x.shape[1], _p(idx), M // frames, H, _p(out), _ld(out),
+                                               frames, _p(order), _stream()), "cofi_neighbor_maxpool_slice")
+    return out
+
+
 def neighbor_maxpool(x, idx, out=None, frames: int = 1, order=None):
     lib = _lib.load()
     _mat(x, "x"), _mat(idx, "idx", torch.int32)
@@ -742,6 +778,14 @@ def neighbor_maxpool(x, idx, out=None, frames: int = 1, order=None):
         out = torch.empty((M, x.shape[1]), dtype=torch.float32, device=x.device)
     if M == 0:
         return out
+    N = x.shape[0] // frames
+    if (frames >= MAXPOOL_SLICE_MIN_FRAMES and N <= MAXPOOL_SLICE_MAX_ROWS and maxpool_slice()
+            and lib.cofi_neighbor_maxpool_slice_ok(N, x.shape[1], H, frames)):
+        rc = lib.cofi_neighbor_maxpool_slice(_p(x), _ld(x), N, x.shape[1], _p(idx), M // frames, H, _p(out), _ld(out), frames, _p(order),
+                                             _stream())
+        if rc != _lib.COFI_EUNSUPPORTED:   # refused after all: the gather kernel
+            _lib.check(rc, "cofi_neighbor_maxpool_slice")
+            return out
     _lib.check(lib.cofi_neighbor_maxpool(_p(x), _ld(x), x.shape[0] // frames, x.shape[1], _p(idx), M // frames, H, _p(out), _ld(out),
                                          frames, _p(order), _stream()), "cofi_neighbor_maxpool")
     return out

@@ -236,6 +236,16 @@ int cofi_kpconv_fused_rec_sorted(const float *feats, int ldf, int N, int C, cons
  * pad row stands behind index N. */
 int cofi_neighbor_maxpool(const float *x, int ldx, int N, int C, const int32_t *idx, int M, int H, float *out, int ldo, int frames,
                           const int32_t *order /* optional, as above */, cofi_stream_t stream);
+/* cofi_neighbor_maxpool for a source that fits a CU's LDS a few channels at a time (the deep stages of a stack-mode submission): one
+ * workgroup per (frame, group of 8 or 4 channels, range of queries) loads the frame's N x 8 (N + 2 <= 3072, C > 4) or N x 4
+ * (N + 2 <= 6144) slice once, coalesced, and serves all H neighbours of its queries from LDS.  Same bits as cofi_neighbor_maxpool (a
+ * maximum is exact in any order) - on every table without the entry INT_MIN: that kernel keeps INT_MIN as its own mark for "past the end
+ * of the row" and ignores such an entry, here it is an index outside [0, N) like any other and lists the zero row.  Any C, ldx, ldo and alignment (16-byte loads and stores where they are aligned); `order` is accepted
+ * and ignored.  COFI_EUNSUPPORTED where the slice does not fit at 4 channels - cofi_neighbor_maxpool_slice_ok(N, C, H, frames) says
+ * (1 / 0) whether a launch would be served. */
+int cofi_neighbor_maxpool_slice_ok(int N, int C, int H, int frames);
+int cofi_neighbor_maxpool_slice(const float *x, int ldx, int N, int C, const int32_t *idx, int M, int H, float *out, int ldo, int frames,
+                                const int32_t *order /* ignored */, cofi_stream_t stream);
 int cofi_gather_rows(const float *x, int ldx, int N, int C, const int32_t *idx, int idx_stride, int M, float *out, int ldo, int frames,
                      cofi_stream_t stream);
 
