@@ -133,7 +133,12 @@ __global__ __launch_bounds__(256) void group_stats_from_colpart_kernel(const flo
         const double ts = (red[0][0] + red[1][0]) + (red[2][0] + red[3][0]), tq = (red[0][1] + red[1][1]) + (red[2][1] + red[3][1]);
         const double mean = ts / count;
         double var = tq / count - mean * mean;
-        if (var < 0.0) var = 0.0;
+        // a group of ONE value (a one-pixel map, one channel per group) has variance 0; its partial holds fl32(x^2), whose rounding error
+        // (up to 2^-25 x^2) would otherwise stand next to eps = 1e-5 and move the REPORTED rstd by up to 0.2 %.  Cosmetic for the
+        // normalisation itself - x - mean is exactly 0 there, whatever rstd - which is why the in-kernel folds of the same partials
+        // (stat_fold.h, cofi_norm_finalize) keep the plain expression.  The cancellation of the one-pass formula remains for any group
+        // whose variance is not far above 2^-24 mean^2.
+        if (var < 0.0 || count == 1.0) var = 0.0;
         stats[2 * g + 0] = (float)mean;
         stats[2 * g + 1] = (float)(1.0 / sqrt(var + (double)eps));
     }

@@ -413,7 +413,12 @@ class Normed:
         return self.stats.desc(self.gamma, self.beta, self.slope)
 
     def materialize(self, out=None, want_row_pos: bool = False):
-        return group_norm_apply(self.y, self.stats, self.gamma, self.beta, slope=self.slope, out=out, frames=self.stats.frames,
+        st = self.stats
+        if st.frames > 1 and (st.M // st.frames) % st.slab_rows:
+            # the producer's slabs straddle frames (63-pixel maps of a stacked batch): the partials mix rows of two frames, so the per-frame
+            # statistics come from a pass over the map itself (one launch for all frames, as image._in_relu)
+            st = group_stats(self.y, st.groups, st.eps, st.frames)
+        return group_norm_apply(self.y, st, self.gamma, self.beta, slope=self.slope, out=out, frames=self.stats.frames,
                                 want_row_pos=want_row_pos)
 
 
@@ -1068,8 +1073,14 @@ def im2col_stem(img, kpad: int = 160):
 
 
 def maxpool3x3s2_nhwc(x, H: int, W: int, frames: int = 1):
-    lib = _lib.load()
+    """x (frames*H*W, C) DENSE (the kernel takes no leading dimension), C % 4 == 0 -> (frames*Ho*Wo, C), Ho, Wo."""
+    _mat(x, "x")
     C = x.shape[1]
+    if frames <= 0 or H <= 0 or W <= 0 or x.shape[0] != frames * H * W:
+        raise _lib.CofiError("maxpool3x3s2_nhwc: x has %d rows, %d frame(s) of %d x %d pixels have %d" % (x.shape[0], frames, H, W, frames * H * W))
+    if C % 4 or not x.is_contiguous():
+        raise _lib.CofiError("maxpool3x3s2_nhwc: expected a dense map of a multiple of 4 channels, got %s stride %s" % (tuple(x.shape), x.stride()))
+    lib = _lib.load()
     Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
     out = torch.empty((frames * Ho * Wo, C), dtype=torch.float32, device=x.device)
     _lib.check(lib.cofi_maxpool3x3s2_nhwc(_p(x), H, W, C, _p(out), frames, _stream()), "cofi_maxpool3x3s2_nhwc")
@@ -1078,9 +1089,12 @@ def maxpool3x3s2_nhwc(x, H: int, W: int, frames: int = 1):
 
 def upsample2x_cat_nhwc(low, h: int, w: int, skip, frames: int = 1):
     """low (frames*h*w, C1), skip (frames*4*h*w, C2) -> (frames*4*h*w, C1+C2)."""
-    lib = _lib.load()
-    _mat(low, "low"), _mat(skip, "skip")
+    _mat(low, "low"), _mat(skip, "skip", device=low.device)
     C1, C2 = low.shape[1], skip.shape[1]
+    if frames <= 0 or h <= 0 or w <= 0 or low.shape[0] != frames * h * w or skip.shape[0] != 4 * frames * h * w:
+        raise _lib.CofiError("upsample2x_cat_nhwc: low has %d rows and skip %d, %d frame(s) of %d x %d pixels have %d and %d"
+                             % (low.shape[0], skip.shape[0], frames, h, w, frames * h * w, 4 * frames * h * w))
+    lib = _lib.load()
     out = torch.empty((frames * 4 * h * w, C1 + C2), dtype=torch.float32, device=low.device)
     _lib.check(lib.cofi_upsample2x_cat_nhwc(_p(low), _ld(low), C1, h, w, _p(skip), _ld(skip), C2, _p(out), _ld(out), frames, _stream()),
                "cofi_upsample2x_cat_nhwc")
