@@ -169,6 +169,12 @@ SIGNATURES = {
     "cofi_radius_mask": (_I, [_P, _P, _I, _I, _I, _F, ctypes.c_longlong, ctypes.c_longlong, _P, _P, _P]),
     "cofi_gather_transform": (_I, [_P, _P, _I, _P, _P, _P, _I, _P]),
     "cofi_resize_crop_image": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
+    "cofi_accumulate_sweeps_workspace": (_Z, [_I]),
+    "cofi_accumulate_sweeps": (_I, [_P, _I, _P, _I, _I, _P, _P, _P, _P, _P, _Z, _P]),
+    "cofi_voxel_downsample_f64_workspace": (_Z, [_I]),
+    "cofi_voxel_downsample_f64": (_I, [_P, _P, _I, ctypes.c_double, _P, _I, _P, _P, _Z, _P]),
+    "cofi_sweeps_to_camera": (_I, [_P, _I, _P, _P, _I, _I, _P, _P, _P]),
+    "cofi_resize_image_u8": (_I, [_P, _I, _I, _I, _I, _I, _P, _P]),
     "cofi_estimate_normals": (_I, [_P, _I, _P, _P, _I, _I, _I, _F, _P, _P, ctypes.c_longlong, ctypes.c_longlong, _P, _P]),
     "cofi_fuse_workspace": (_Z, [_I, _I, _I]),
     "cofi_fuse_cloud_image": (_I, [_P, _I, _I, _I, _P, _I, _I, _I, _P, _I, _P, _I, _P, _F, _F, _I, _F, _F, _P, _Z, _P, _P, _P, _P, _P, _P, _P]),

@@ -3,6 +3,11 @@
 //   cofi_voxel_downsample   data/kitti.py:145-166  open3d voxel_down_sample(0.1) of points + intensity ("colors") + normals
 //   cofi_gather_transform   data/kitti.py:168-180, 284-288, 293  resample to exactly num_pc rows, random SE(3), feats = [intensity | R n]
 //   cofi_resize_crop_image  data/kitti.py:306-322, 375  cv2.resize(INTER_LINEAR) x0.5, crop, / 255, HWC -> CHW
+// and, for raw nuScenes sweeps (data/build_nuscenes/build_dataset.py; cofii2p_amd/sweeps.py):
+//   cofi_accumulate_sweeps     :109-185  ego-box cut + accumulation into the key sweep's frame, float64, stable compaction
+//   cofi_voxel_downsample_f64  :41-54    voxel_down_sample(0.2) keyed on the float64 points, with reflectance (sort and head scan shared)
+//   cofi_sweeps_to_camera      :265-280  camera frame + in-picture count
+//   cofi_resize_image_u8       :252-260  top rows dropped, cv2.resize(INTER_LINEAR) x0.4, uint8 HWC
 // The KNN pyramid (preprocess_data.py:36-107) is knn_grid.hip; the coarse / fine label projection works on 1280 points and stays
 // host-side numpy, exactly as the reference writes it (cofii2p_amd/dataside.py).
 //
@@ -489,6 +494,249 @@ __global__ void cj_op_kernel(float *img, int P, int op, float factor, int shift,
     img[2 * P + p] = (float)b / 255.f;
 }
 
+// ---- raw nuScenes sweeps (data/build_nuscenes/build_dataset.py) --------------------------------------------------------------------
+// :115-121: a point on the ego vehicle, float32 compares in the sweep's own frame
+__device__ __forceinline__ bool sweep_on_ego(float x, float y) { return (x < 0.8f) & (x > -0.8f) & (y < 2.7f) & (y > -2.7f); }
+
+// kept rows of one RED_T-row chunk of the concatenated sweeps
+__global__ __launch_bounds__(RED_T) void sweep_keep_count_kernel(const float *rows, int ld, int total, int *chunk_keep) {
+    __shared__ int red[RED_T / 64];
+    const int i = blockIdx.x * RED_T + threadIdx.x;
+    const int k = (i < total && !sweep_on_ego(rows[(size_t)i * ld], rows[(size_t)i * ld + 1])) ? 1 : 0;
+    const int c = __popcll(__ballot(k));
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = c;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int s = 0;
+        for (int w = 0; w < RED_T / 64; ++w) s += red[w];
+        chunk_keep[blockIdx.x] = s;
+    }
+}
+
+// :127-185: kept rows in sweep order, then original order (stable compaction: chunk offsets + ballot ranks).  Sweep 0 is widened
+// untransformed, sweep j > 0 goes through T_j in double: s = T[a][0] * x; s = s + T[a][1] * y; s = s + T[a][2] * z; s = s + T[a][3].
+__global__ __launch_bounds__(RED_T) void sweep_write_kernel(const float *rows, int ld, const int32_t *offsets, int S, int total, const double *T,
+                                                           const int *chunk_keep, int nchunk, double *pts, float *inten, int32_t *count_dev) {
+    __shared__ int red[RED_T / 64];
+    __shared__ int s_before;
+    __shared__ int s_off[64];
+    if ((int)threadIdx.x < S) s_off[threadIdx.x] = offsets[threadIdx.x];
+    int part = 0;
+    for (int c = threadIdx.x; c < (int)blockIdx.x; c += RED_T) part += chunk_keep[c];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) part += __shfl_xor(part, o, 64);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = part;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int s = 0;
+        for (int k = 0; k < RED_T / 64; ++k) s += red[k];
+        s_before = s;
+    }
+    __syncthreads();
+    const int before = s_before;
+    __syncthreads();
+    const int i = blockIdx.x * RED_T + threadIdx.x;
+    float x = 0.f, y = 0.f, z = 0.f, r = 0.f;
+    int keep = 0;
+    if (i < total) {
+        const float *p = rows + (size_t)i * ld;
+        x = p[0]; y = p[1]; z = p[2]; r = p[3];
+        keep = !sweep_on_ego(x, y);
+    }
+    const unsigned long long bal = __ballot(keep);
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    if (lane == 0) red[w] = __popcll(bal);
+    __syncthreads();
+    int woff = before;
+    for (int k = 0; k < w; ++k) woff += red[k];
+    if (keep) {
+        int lo = 0, hi = S - 1;   // the sweep of row i: the last j with offsets[j] <= i (empty sweeps share an offset with their successor)
+        while (lo < hi) {
+            const int mid = (lo + hi + 1) >> 1;
+            if (s_off[mid] <= i) lo = mid; else hi = mid - 1;
+        }
+        const size_t o = (size_t)(woff + __popcll(bal & ((1ull << lane) - 1ull)));
+        const double dx = (double)x, dy = (double)y, dz = (double)z;
+        if (lo == 0) {
+            pts[3 * o] = dx; pts[3 * o + 1] = dy; pts[3 * o + 2] = dz;
+        } else {
+            const double *M = T + (size_t)lo * 16;
+#pragma unroll
+            for (int a = 0; a < 3; ++a) {
+                double s = M[4 * a] * dx;
+                s = s + M[4 * a + 1] * dy;
+                s = s + M[4 * a + 2] * dz;
+                s = s + M[4 * a + 3];
+                pts[3 * o + a] = s;
+            }
+        }
+        inten[o] = r;
+    }
+    if ((int)blockIdx.x == nchunk - 1 && threadIdx.x == 0) {
+        int t = before;
+        for (int k = 0; k < RED_T / 64; ++k) t += red[k];
+        count_dev[0] = t;
+    }
+}
+
+// float64 points: bounding box minimum (double) + intensity maximum of one RED_T-row chunk -> part[4 * block ..] = {min x, min y, min z, max
+// intensity widened}
+__global__ __launch_bounds__(RED_T) void vox_bounds_f64_kernel(const double *pts, const float *inten, int N, double *part) {
+    __shared__ double red[4][RED_T / 64];
+    const int i = blockIdx.x * RED_T + threadIdx.x;
+    double mn[3] = {(double)INFINITY, (double)INFINITY, (double)INFINITY};
+    float mx = -INFINITY;
+    if (i < N) {
+#pragma unroll
+        for (int a = 0; a < 3; ++a) mn[a] = pts[(size_t)i * 3 + a];
+        mx = inten[i];
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+#pragma unroll
+        for (int a = 0; a < 3; ++a) mn[a] = fmin(mn[a], __shfl_xor(mn[a], o, 64));
+        mx = fmaxf(mx, __shfl_xor(mx, o, 64));
+    }
+    const int w = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) { red[0][w] = mn[0]; red[1][w] = mn[1]; red[2][w] = mn[2]; red[3][w] = (double)mx; }
+    __syncthreads();
+    if (threadIdx.x < 4) {
+        double v = red[threadIdx.x][0];
+        for (int k = 1; k < RED_T / 64; ++k) v = threadIdx.x < 3 ? fmin(v, red[threadIdx.x][k]) : fmax(v, red[threadIdx.x][k]);
+        part[4 * blockIdx.x + threadIdx.x] = v;
+    }
+}
+
+// vox_keys_kernel on float64 points: the point is NOT rounded to float32 before floor((p - minb) / voxel) (build_dataset.py:41-54 hands
+// open3d the float64 array)
+__global__ __launch_bounds__(256) void vox_keys_f64_kernel(const double *pts, int N, double voxel, const double *part, int nchunk, VoxHeader *hdr,
+                                                          unsigned long long *keys, int *idx) {
+    __shared__ double red[4][4];
+    __shared__ double s_minb[3];
+    double mn[3] = {(double)INFINITY, (double)INFINITY, (double)INFINITY}, mx = -(double)INFINITY;
+    for (int c = threadIdx.x; c < nchunk; c += 256) {
+        const double *v = part + 4 * c;
+        mn[0] = fmin(mn[0], v[0]); mn[1] = fmin(mn[1], v[1]); mn[2] = fmin(mn[2], v[2]); mx = fmax(mx, v[3]);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+#pragma unroll
+        for (int a = 0; a < 3; ++a) mn[a] = fmin(mn[a], __shfl_xor(mn[a], o, 64));
+        mx = fmax(mx, __shfl_xor(mx, o, 64));
+    }
+    const int w = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) { red[0][w] = mn[0]; red[1][w] = mn[1]; red[2][w] = mn[2]; red[3][w] = mx; }
+    __syncthreads();
+    if (threadIdx.x < 3) {
+        const int a = threadIdx.x;
+        const double m = fmin(fmin(red[a][0], red[a][1]), fmin(red[a][2], red[a][3]));
+        s_minb[a] = m - voxel * 0.5;
+        if (blockIdx.x == 0) hdr->minb[a] = s_minb[a];
+    }
+    if (threadIdx.x == 3 && blockIdx.x == 0) hdr->imax = (float)fmax(fmax(red[3][0], red[3][1]), fmax(red[3][2], red[3][3]));
+    __syncthreads();
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= N) return;
+    unsigned long long key = 0;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        const double r = (pts[(size_t)i * 3 + a] - s_minb[a]) / voxel;
+        long long v = (long long)floor(r);
+        if (v < 0 || v >= (1 << KEY_BITS)) { hdr->overflow = 1; v = v < 0 ? 0 : (1 << KEY_BITS) - 1; }
+        key = (key << KEY_BITS) | (unsigned long long)v;
+    }
+    keys[i] = key;
+    idx[i] = i;
+}
+
+// out row v = [float32(mean xyz) | float32(mean(float32(intensity / imax)) * (double)imax)], 4 floats.  build_dataset.py:52 multiplies the
+// float64 colour by the float32 maximum in double and :227 casts afterwards - not the float32 product of vox_mean_kernel.
+__global__ void vox_mean_f64_kernel(const double *pts, const float *inten, const int *sorted_idx, const int *head_pos, const VoxHeader *hdr, int N,
+                                    int cap, float *out) {
+    const int v = blockIdx.x * blockDim.x + threadIdx.x;
+    const int nv = hdr->nvox;
+    if (v >= nv || v >= cap) return;
+    const int b = head_pos[v], e = v + 1 < nv ? head_pos[v + 1] : N;
+    double acc[4] = {0, 0, 0, 0};
+    const float imax = hdr->imax;
+    for (int s = b; s < e; ++s) {
+        const int i = sorted_idx[s];
+#pragma unroll
+        for (int a = 0; a < 3; ++a) acc[a] += pts[(size_t)i * 3 + a];
+        acc[3] += (double)(inten[i] / imax);
+    }
+    const double inv = 1.0 / (double)(e - b);
+    f32x4 o;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) o[a] = (float)(acc[a] * inv);
+    o[3] = (float)((acc[3] * inv) * (double)imax);
+    *reinterpret_cast<f32x4 *>(out + (size_t)v * 4) = o;
+}
+
+// :265-280: c = R p + t (float64 P_cam_pc, float32 point widened), uvz = K c (float32 K widened), each a chain of separate double products
+// and sums in the order k = 0, 1, 2 (, t); in the picture = depth > 0 and 0 <= u <= W - 1 and 0 <= v <= H - 1.  Cloud out channel-major.
+__global__ __launch_bounds__(256) void sweeps_camera_kernel(const float *rows4, int M, const double *P, const float *K, int H, int W, float *out,
+                                                           int32_t *inside) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    bool in = false;
+    if (i < M) {
+        const f32x4 r = *reinterpret_cast<const f32x4 *>(rows4 + (size_t)i * 4);
+        const double x = (double)r[0], y = (double)r[1], z = (double)r[2];
+        double c[3], uvz[3];
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            double s = P[4 * a] * x;
+            s = s + P[4 * a + 1] * y;
+            s = s + P[4 * a + 2] * z;
+            s = s + P[4 * a + 3];
+            c[a] = s;
+            out[(size_t)a * M + i] = (float)s;
+        }
+        out[(size_t)3 * M + i] = r[3];
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            double s = (double)K[3 * a] * c[0];
+            s = s + (double)K[3 * a + 1] * c[1];
+            s = s + (double)K[3 * a + 2] * c[2];
+            uvz[a] = s;
+        }
+        if (uvz[2] > 0.0) {
+            const double u = uvz[0] / uvz[2], v = uvz[1] / uvz[2];
+            in = u >= 0.0 && u <= (double)(W - 1) && v >= 0.0 && v <= (double)(H - 1);
+        }
+    }
+    const int cnt = __popcll(__ballot(in));
+    if ((threadIdx.x & 63) == 0 && cnt) atomicAdd(inside, cnt);   // integer: order-free
+}
+
+// build_dataset.py:252-260: rows [top, sh) of the uint8 HWC image through cv2.resize(INTER_LINEAR), the arithmetic of resize_crop_kernel,
+// the clamped integer stored as uint8 HWC.  One thread per output value.
+__global__ void resize_u8_kernel(const uint8_t *src, int sh, int sw, int dh, int dw, uint8_t *out) {
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= 3 * dh * dw) return;
+    const int c = e % 3, dx = (e / 3) % dw, dy = e / (3 * dw);
+    const float scale_x = (float)((double)sw / dw), scale_y = (float)((double)sh / dh);
+    auto coef = [](int d, float scale, int ssize, int &s0, int &a0, int &a1) {
+        float f = (float)((d + 0.5) * (double)scale - 0.5);
+        int s = (int)floorf(f);
+        f -= s;
+        if (s < 0) { f = 0.f; s = 0; }
+        if (s >= ssize - 1) { f = 0.f; s = ssize - 1; }
+        s0 = s;
+        a0 = (int)rintf((1.f - f) * 2048.f);
+        a1 = (int)rintf(f * 2048.f);
+    };
+    int sx, ax0, ax1, sy, ay0, ay1;
+    coef(dx, scale_x, sw, sx, ax0, ax1);
+    coef(dy, scale_y, sh, sy, ay0, ay1);
+    const int sx1 = min(sx + 1, sw - 1), sy1 = min(sy + 1, sh - 1);
+    auto px = [&](int yy, int xx) { return (int)src[((size_t)yy * sw + xx) * 3 + c]; };
+    const int r0 = px(sy, sx) * ax0 + px(sy, sx1) * ax1;
+    const int r1 = px(sy1, sx) * ax0 + px(sy1, sx1) * ax1;
+    const int v = (((ay0 * (r0 >> 4)) >> 16) + ((ay1 * (r1 >> 4)) >> 16) + 2) >> 2;
+    out[e] = (uint8_t)min(max(v, 0), 255);
+}
+
 }  // namespace
 
 static inline size_t vox_align(size_t v) { return (v + 255) & ~(size_t)255; }
@@ -624,5 +872,87 @@ extern "C" int cofi_color_jitter_chw(float *img, int H, int W, const int *order4
         }
         hipLaunchKernelGGL(cj_op_kernel, dim3(cofi_cdiv(P, 256)), dim3(256), 0, s, img, P, op, fac[op], shift, (const unsigned long long *)ws);
     }
+    return cofi_launch_status();
+}
+
+// ---- raw nuScenes sweeps: accumulate -> float64 voxel grid -> camera frame, and the image (build_dataset.py:109-185, 41-54, 252-280) --------
+extern "C" size_t cofi_accumulate_sweeps_workspace(int total_rows) {
+    if (total_rows <= 0) return 0;
+    return vox_align((size_t)cofi_cdiv(total_rows, RED_T) * 4);   // kept rows per 1024-row chunk
+}
+
+extern "C" int cofi_accumulate_sweeps(const float *rows, int ld, const int32_t *offsets_dev, int S, int total_rows, const double *T_dev,
+                                      double *points, float *intensity, int32_t *count_dev, void *ws, size_t ws_bytes, cofi_stream_t stream) {
+    if (!rows || !offsets_dev || !T_dev || !points || !intensity || !count_dev || (ld != 4 && ld != 5) || S <= 0 || S > 64 || total_rows <= 0)
+        return COFI_EINVAL;
+    if (((uintptr_t)T_dev & 7) || ((uintptr_t)points & 7)) return COFI_EINVAL;
+    if (!ws || ws_bytes < cofi_accumulate_sweeps_workspace(total_rows) || ((uintptr_t)ws & 15)) return COFI_EWORKSPACE;
+    hipStream_t s = cofi_s(stream);
+    const int nchunk = cofi_cdiv(total_rows, RED_T);
+    int *keep = (int *)ws;
+    hipLaunchKernelGGL(sweep_keep_count_kernel, dim3(nchunk), dim3(RED_T), 0, s, rows, ld, total_rows, keep);
+    hipLaunchKernelGGL(sweep_write_kernel, dim3(nchunk), dim3(RED_T), 0, s, rows, ld, offsets_dev, S, total_rows, T_dev, keep, nchunk, points, intensity,
+                       count_dev);
+    return cofi_launch_status();
+}
+
+extern "C" size_t cofi_voxel_downsample_f64_workspace(int N) {
+    if (N <= 0) return 0;
+    // as cofi_voxel_downsample_workspace, with 4 doubles of bounds per chunk
+    const size_t nchunk = (size_t)cofi_cdiv(N, RED_T);
+    return 256 + vox_align(nchunk * 32) + vox_align(nchunk * 4) + vox_align((size_t)(256 * SORT_TILES + 256) * 4) + 2 * vox_align((size_t)N * 8) +
+           3 * vox_align((size_t)N * 4);
+}
+
+extern "C" int cofi_voxel_downsample_f64(const double *points, const float *intensity, int N, double voxel, float *out_rows4, int cap,
+                                         int32_t *count_dev, void *ws, size_t ws_bytes, cofi_stream_t stream) {
+    if (!points || !intensity || !out_rows4 || !count_dev || N <= 0 || !(voxel > 0.0) || cap <= 0) return COFI_EINVAL;
+    if (((uintptr_t)points & 7) || ((uintptr_t)out_rows4 & 15)) return COFI_EINVAL;
+    if (!ws || ws_bytes < cofi_voxel_downsample_f64_workspace(N) || ((uintptr_t)ws & 15)) return COFI_EWORKSPACE;
+    hipStream_t s = cofi_s(stream);
+    const int nchunk = cofi_cdiv(N, RED_T);
+    char *w = (char *)ws;
+    VoxHeader *hdr = (VoxHeader *)w; w += 256;
+    double *bpart = (double *)w; w += vox_align((size_t)nchunk * 32);
+    int *hpart = (int *)w; w += vox_align((size_t)nchunk * 4);
+    int *hist = (int *)w, *tot = hist + 256 * SORT_TILES; w += vox_align((size_t)(256 * SORT_TILES + 256) * 4);
+    unsigned long long *kA = (unsigned long long *)w; w += vox_align((size_t)N * 8);
+    unsigned long long *kB = (unsigned long long *)w; w += vox_align((size_t)N * 8);
+    int *vA = (int *)w; w += vox_align((size_t)N * 4);
+    int *vB = (int *)w; w += vox_align((size_t)N * 4);
+    int *heads = (int *)w;
+    (void)hipMemsetAsync(hdr, 0, sizeof(VoxHeader), s);
+    hipLaunchKernelGGL(vox_bounds_f64_kernel, dim3(nchunk), dim3(RED_T), 0, s, points, intensity, N, bpart);
+    hipLaunchKernelGGL(vox_keys_f64_kernel, dim3(cofi_cdiv(N, 256)), dim3(256), 0, s, points, N, voxel, bpart, nchunk, hdr, kA, vA);
+    const int tile = cofi_cdiv(N, SORT_TILES);
+    for (int pass = 0; pass < SORT_PASSES; ++pass) {
+        hipLaunchKernelGGL(sort_hist_kernel, dim3(SORT_TILES / SORT_WPB), dim3(64 * SORT_WPB), 0, s, kA, N, 8 * pass, tile, hist);
+        hipLaunchKernelGGL(sort_scan_kernel, dim3(64), dim3(256), 0, s, hist, tot);
+        hipLaunchKernelGGL(sort_scatter_kernel, dim3(SORT_TILES / SORT_WPB), dim3(64 * SORT_WPB), 0, s, kA, vA, kB, vB, N, 8 * pass, tile, hist, tot);
+        unsigned long long *tk = kA; kA = kB; kB = tk;
+        int *tv = vA; vA = vB; vB = tv;
+    }
+    hipLaunchKernelGGL(vox_head_count_kernel, dim3(nchunk), dim3(RED_T), 0, s, kA, N, hpart);
+    hipLaunchKernelGGL(vox_head_write_kernel, dim3(nchunk), dim3(RED_T), 0, s, kA, N, hpart, nchunk, heads, hdr, count_dev);
+    hipLaunchKernelGGL(vox_mean_f64_kernel, dim3(cofi_cdiv(N, 256)), dim3(256), 0, s, points, intensity, vA, heads, hdr, N, cap, out_rows4);
+    return cofi_launch_status();
+}
+
+extern "C" int cofi_sweeps_to_camera(const float *rows4, int M, const double *P44_dev, const float *K33_dev, int H, int W, float *out_4m,
+                                     int32_t *inside_dev, cofi_stream_t stream) {
+    if (!rows4 || !P44_dev || !K33_dev || !out_4m || !inside_dev || M <= 0 || H <= 0 || W <= 0) return COFI_EINVAL;
+    if (((uintptr_t)rows4 & 15) || ((uintptr_t)P44_dev & 7)) return COFI_EINVAL;
+    hipStream_t s = cofi_s(stream);
+    if (hipError_t e = hipMemsetAsync(inside_dev, 0, sizeof(int32_t), s); e != hipSuccess) return (int)e;
+    hipLaunchKernelGGL(sweeps_camera_kernel, dim3(cofi_cdiv(M, 256)), dim3(256), 0, s, rows4, M, P44_dev, K33_dev, H, W, out_4m, inside_dev);
+    return cofi_launch_status();
+}
+
+extern "C" int cofi_resize_image_u8(const uint8_t *src_hwc, int src_h, int src_w, int top_rows, int dst_h, int dst_w, uint8_t *dst_hwc,
+                                    cofi_stream_t stream) {
+    if (!src_hwc || !dst_hwc || src_h <= 0 || src_w <= 0 || top_rows < 0 || top_rows >= src_h || dst_h <= 0 || dst_w <= 0) return COFI_EINVAL;
+    if ((long long)dst_h * dst_w * 3 > 0x7fffffffLL || (long long)src_h * src_w * 3 > 0x7fffffffLL) return COFI_EINVAL;
+    hipLaunchKernelGGL(resize_u8_kernel, dim3(cofi_cdiv(3 * dst_h * dst_w, 256)), dim3(256), 0, cofi_s(stream), src_hwc + (size_t)top_rows * src_w * 3,
+                       src_h - top_rows, src_w, dst_h, dst_w, dst_hwc);
     return cofi_launch_status();
 }

@@ -152,3 +152,71 @@ def make_raw_nuscenes(frame_id: int = 0, num_points: int = 26000, img_hw=(900, 1
     inten = g.uniform(0.0, 255.0, (num_points, 1))
     K = np.array([[1266.417, 0.0, 816.267], [0.0, 1266.417, 491.507], [0.0, 0.0, 1.0]])
     return np.ascontiguousarray(np.concatenate([pts, inten], 1).T.astype(np.float32)), img, K
+
+
+def _quat_wxyz(yaw=0.0, pitch=0.0, roll=0.0):
+    """unit quaternion (w, x, y, z) of Rz(yaw) Ry(pitch) Rx(roll)"""
+    cy, sy, cp, sp, cr, sr = np.cos(yaw / 2), np.sin(yaw / 2), np.cos(pitch / 2), np.sin(pitch / 2), np.cos(roll / 2), np.sin(roll / 2)
+    return np.array([cr * cp * cy + sr * sp * sy, sr * cp * cy - cr * sp * sy, cr * sp * cy + sr * cp * sy, cr * cp * sy - sr * sp * cy])
+
+
+def _quat_matrix(q):
+    w, x, y, z = q / np.linalg.norm(q)
+    return np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w)],
+                     [2 * (x * y + z * w), 1 - 2 * (x * x + z * z), 2 * (y * z - x * w)],
+                     [2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)]])
+
+
+def make_raw_sweeps(frame_id: int = 0, sweeps: int = 7, points_per_sweep: int = 34700, img_hw=(900, 1600), ld: int = 5, blind_first: bool = False):
+    """One raw nuScenes-style sample as data/build_nuscenes/build_dataset.py:109-185, 239-268 reads it from the devkit: `sweeps` lidar
+    sweeps, the key sweep first, then those the accumulation walk picks (later ones, then earlier ones), each (n, ld) float32 rows
+    [x y z intensity (ring)] in ITS OWN lidar frame (x right, y forward, z up), taken from a vehicle that drives along the world's x axis -
+    2 m between picked sweeps, a little yaw - over one shared scene (ground plane, four long facades), so the sweeps align once they are
+    brought into the key sweep's frame.  The ground is sampled with 1 / r density from 0.5 m on: some points of every sweep fall into the
+    ego box |x| < 0.8, |y| < 2.7.  Poses are (quaternion wxyz, translation) records as the devkit stores them.
+    Returns {"sweeps": [...], "ego_poses": [(q, t)] per sweep, "lidar_calib": (q, t), "cameras": [{"img" (H, W, 3) uint8, "K" (3, 3)
+    float32, "ego_pose": (q, t), "calib": (q, t)}]}: the front camera at the key sweep's time and once more 0.25 m further on; with
+    blind_first a camera that looks away from the whole scene comes first, so that the in-picture threshold rejects it."""
+    g = np.random.default_rng(31337 + int(frame_id))
+    H, W = img_hw
+    lidar_calib = (_quat_wxyz(yaw=-np.pi / 2), np.array([0.94, 0.0, 1.84]))       # lidar y = vehicle x (forward)
+    cam_calib = (np.array([0.5, -0.5, 0.5, -0.5]), np.array([1.70, 0.01, 1.51]))  # camera z = vehicle x, camera x = vehicle -y, camera y = vehicle -z
+    R_vl = _quat_matrix(lidar_calib[0])
+    later = sweeps // 2                                        # 7 sweeps: the key sweep, 3 later, 3 earlier
+    steps = [0] + list(range(1, later + 1)) + [-k for k in range(1, sweeps - later)]
+    walls = [(0, 14.0), (0, -11.0), (1, 38.0), (1, -33.0)]     # (axis the facade is normal to: 0 = world y, 1 = world x; offset)
+    out, poses = [], []
+    for step in steps:
+        yaw = 0.004 * step + g.normal(0.0, 0.001)
+        pos = np.array([2.0 * step + g.normal(0.0, 0.02), 0.05 * step, 0.0])
+        q = _quat_wxyz(yaw=yaw)
+        R_wv = _quat_matrix(q)
+        sensor = pos + R_wv @ lidar_calib[1]
+        n_ground = int(0.6 * points_per_sweep)
+        r = np.exp(g.uniform(np.log(0.5), np.log(70.0), n_ground))
+        az = g.uniform(-np.pi, np.pi, n_ground)
+        ground = np.stack([sensor[0] + r * np.cos(az), sensor[1] + r * np.sin(az), g.normal(0.0, 0.02, n_ground)], 1)
+        n_wall = points_per_sweep - n_ground
+        side = g.integers(0, 4, n_wall)
+        u = g.uniform(-60.0, 60.0, n_wall) * g.uniform(0.15, 1.0, n_wall)
+        h = g.uniform(0.0, 7.0, n_wall)
+        off = np.array([w[1] for w in walls])[side] + g.normal(0.0, 0.02, n_wall)
+        across = np.array([w[0] for w in walls])[side] == 0
+        wall = np.where(across[:, None], np.stack([sensor[0] + u, off, h], 1), np.stack([off, sensor[1] + u, h], 1))
+        world = np.concatenate([ground, wall], 0)[g.permutation(points_per_sweep)]
+        veh = (world - pos) @ R_wv               # R_wv^T (world - pos)
+        lid = (veh - lidar_calib[1]) @ R_vl
+        cols = [lid, g.uniform(0.0, 255.0, (points_per_sweep, 1))]
+        if ld == 5:
+            cols.append(g.integers(0, 32, (points_per_sweep, 1)).astype(np.float64))
+        out.append(np.ascontiguousarray(np.concatenate(cols, 1).astype(np.float32)))
+        poses.append((q, pos))
+    K = np.array([[1266.417, 0.0, 816.267], [0.0, 1266.417, 491.507], [0.0, 0.0, 1.0]], dtype=np.float32)
+    cams = []
+    if blind_first:
+        cams.append({"img": g.integers(0, 256, (H, W, 3), dtype=np.uint8), "K": K.copy(), "ego_pose": (_quat_wxyz(yaw=np.pi), np.array([-300.0, 0.0, 0.0])),
+                     "calib": cam_calib})
+    for dx in (0.0, 0.25):
+        cams.append({"img": g.integers(0, 256, (H, W, 3), dtype=np.uint8), "K": K.copy(), "ego_pose": (poses[0][0], poses[0][1] + np.array([dx, 0.0, 0.0])),
+                     "calib": cam_calib})
+    return {"sweeps": out, "ego_poses": poses, "lidar_calib": lidar_calib, "cameras": cams}

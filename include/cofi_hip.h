@@ -807,6 +807,39 @@ int cofi_gather_transform(const float *vox_rows, const int32_t *choice, int n, c
                           cofi_stream_t stream);
 int cofi_resize_crop_image(const uint8_t *src_hwc, int src_h, int src_w, int dst_h, int dst_w, int crop_y, int crop_x, int H, int W,
                            float *out_chw, cofi_stream_t stream);
+/* Raw nuScenes sweeps -> the stored sample FramePreparer(dataset='nuscenes') takes (data/build_nuscenes/build_dataset.py:41-54, 109-185,
+ * 217-300; cofii2p_amd/sweeps.py).  Every floating-point result is a chain of separate correctly rounded products and sums in the stated
+ * order (no contraction), so tests/sweeps_refs.py restates it bit for bit; parity with open3d, cv2 and pyquaternion is unpinned.
+ *   cofi_accumulate_sweeps   rows (total_rows, ld) float32, ld = 5 (.pcd.bin: x y z intensity ring) or 4: the S <= 64 sweeps back to back,
+ *       sweep j at rows offsets_dev[j] .. offsets_dev[j + 1] (S + 1 int32 in device memory, offsets[0] = 0, offsets[S] = total_rows, empty
+ *       sweeps allowed); T_dev (S, 4, 4) float64 row-major, sweep j -> key sweep (entry 0 is not read).  A row is dropped iff
+ *       (x < 0.8f) & (x > -0.8f) & (y < 2.7f) & (y > -2.7f) in its own frame (:115-121); the others come out in input order (stable
+ *       compaction: chunk counts, scan, ordered writes - no float atomics): points (total_rows, 3) float64 = the widened row for sweep 0,
+ *       s = T[a][0] * x; s = s + T[a][1] * y; s = s + T[a][2] * z; s = s + T[a][3] in double for the others; intensity (total_rows) float32;
+ *       count_dev[0] = rows kept.  ws = cofi_accumulate_sweeps_workspace(total_rows), 16-byte aligned.
+ *   cofi_voxel_downsample_f64  cofi_voxel_downsample on float64 points (N, 3) + float32 intensity (N): the voxel index is taken from the
+ *       float64 point (not from its float32 rounding), means in double in input order times 1.0 / count, out_rows4 (cap, 4) float32 =
+ *       [float32(mean) | float32(mean(float32(intensity / max)) * (double)max)] (:52 multiplies in double, :227 casts afterwards) in
+ *       ascending (ix, iy, iz) order; count_dev[0] = voxels (may exceed cap: the first cap rows are written), count_dev[1] = 1 if an index
+ *       overflowed 13 bits.  ws = cofi_voxel_downsample_f64_workspace(N), 16-byte aligned; out_rows4 16-byte aligned.
+ *   cofi_sweeps_to_camera    rows4 (M, 4) -> out_4m (4, M) float32 channel-major = [float32(c) | intensity], c = R p + t with P44_dev the
+ *       float64 4x4 P_cam_pc and p widened, s = R[a][0] * x; s = s + R[a][1] * y; s = s + R[a][2] * z; s = s + t[a]; uvz = K c with K33_dev
+ *       float32 widened, same order, no translation.  inside_dev[0] (zeroed by the call, integer atomics) = rows with uvz[2] > 0 and
+ *       0 <= uvz[0] / uvz[2] <= W - 1 and 0 <= uvz[1] / uvz[2] <= H - 1 (:270-280).
+ *   cofi_resize_image_u8     rows [top_rows, src_h) of the uint8 HWC image through cv2.resize(INTER_LINEAR) to (dst_h, dst_w), the fixed-point
+ *       arithmetic of cofi_resize_crop_image, stored as uint8 HWC (:252-260).
+ * COFI_EINVAL: NULL or misaligned operand, ld not 4 or 5, S outside 1..64, non-positive sizes, top_rows outside [0, src_h);
+ * COFI_EWORKSPACE: ws NULL, misaligned or too small. */
+size_t cofi_accumulate_sweeps_workspace(int total_rows);
+int cofi_accumulate_sweeps(const float *rows, int ld, const int32_t *offsets_dev, int S, int total_rows, const double *T_dev, double *points,
+                           float *intensity, int32_t *count_dev, void *ws, size_t ws_bytes, cofi_stream_t stream);
+size_t cofi_voxel_downsample_f64_workspace(int N);
+int cofi_voxel_downsample_f64(const double *points, const float *intensity, int N, double voxel, float *out_rows4, int cap, int32_t *count_dev,
+                              void *ws, size_t ws_bytes, cofi_stream_t stream);
+int cofi_sweeps_to_camera(const float *rows4, int M, const double *P44_dev, const float *K33_dev, int H, int W, float *out_4m,
+                          int32_t *inside_dev, cofi_stream_t stream);
+int cofi_resize_image_u8(const uint8_t *src_hwc, int src_h, int src_w, int top_rows, int dst_h, int dst_w, uint8_t *dst_hwc,
+                         cofi_stream_t stream);
 /* Surface normals for a scan that comes without them (a velodyne .bin, a live scan): the reference reads the normal from its
  * pc_npy_with_normal file (kitti.py:130) and computes it nowhere, so this contract is the project's own; parity with the third-party
  * estimator of the upstream preprocessing is unpinned.
