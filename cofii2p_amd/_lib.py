@@ -148,6 +148,10 @@ SIGNATURES = {
     "cofi_pnp_ransac_rig_workspace": (_Z, [_I, _I]),
     "cofi_pnp_ransac_rig": (_I, [_P, _I, _P, _I, _I, _P, _I, _P, _P, _I, _I, _I, _I, _I, _F, ctypes.c_uint, _I, _P, _Z, _P, _P, _P, _P, _P, _P]),
     "cofi_pose_errors": (_I, [_P, _P, _I, _I, _P, _P]),
+    "cofi_pose_covariance": (_I, [_P, _P, _P, _I, _F, _F, _F, _F, _P, _P, _P, _F, _P, _P, _P, _P]),
+    "cofi_pose_covariance_batch": (_I, [_P, _I, _P, _I, _I, _P, _I, _P, _I, _I, _P, _P, _P, _F, _P, _P, _P, _P]),
+    "cofi_pose_covariance_rig": (_I, [_P, _I, _P, _I, _I, _P, _I, _P, _P, _I, _I, _I, _I, _P, _P, _P, _F, _P, _P, _P, _P]),
+    "cofi_pose_nees": (_I, [_P, _P, _I, _P, _P, _I, _P, _P]),
     "cofi_eval_monitors": (_I, [_P, _I, _P, _I, _I, _P, _I, _P, _I, _I, _P, _P, _P, _I, _P, _I, _P, _P, _I, _P]),
     "cofi_val_gather": (_I, [_P, _I, _I, _I, _I, _P, _I, _I, _P, _P, _I, _I, _I, _P, _P, _P]),
     "cofi_val_monitors_workspace": (_Z, [_I, _I]),

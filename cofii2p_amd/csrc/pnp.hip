@@ -21,6 +21,8 @@
 //   copies, so the per-frame and batched kernels compute what they always did.  A rig hypothesis is a P3P solve in ONE camera (drawn in
 //   proportion to the cameras' rows) carried into the rig frame through that camera's extrinsics; it is scored and refitted over ALL cameras.
 // Kernel 3 (pose_errors_kernel): RTE / RRE of B poses against ground truth, one thread per frame, fp64.
+// Kernel 4 (covariance_body behind cofi_pose_covariance, _batch, _rig): the 6x6 covariance and information matrix of a returned pose from
+//   the refit's own normal equations over the consensus set, one wave per body; pose_nees_kernel scores it against ground truth.
 #include <type_traits>
 
 #include "common.h"
@@ -773,6 +775,188 @@ __global__ __launch_bounds__(256) void pnp_refine_rig_kernel(RigOperands rig, in
                      poses + (size_t)s * iters * 12, best_keys + s, lm_iters);
 }
 
+// ---- pose covariance: the Gauss-Newton covariance of the refit's least-squares problem at the pose that was RETURNED (float32), over the
+// consensus set the solver wrote into the masks.  H = sum J^T J and cost = sum |r|^2 through accumulate / accumulate_rig, sigma^2 =
+// cost / (2 n - 6) (or the caller's), info = H / sigma^2, cov = sigma^2 H^-1 by a Cholesky factorisation of the unit-diagonal
+// D^-1/2 H D^-1/2.  One wave per body, no LDS, no barrier: camera-major, lane-strided partials, wave_sum_d; lane 0 factorises and stores.
+constexpr int COV_WAVES = 4;   // bodies per workgroup of the batched and the rig kernel
+
+// What the covariance body works on: the scored cameras of the body (usable intrinsics), their rows, masks and row Jacobians.
+struct FrameCovView {
+    CorrGlobal corr_;
+    int n;
+    Cam cam_;
+    const uint8_t *mask_;
+    struct Camera {
+        CorrGlobal corr;
+        int n;
+        Cam cam;
+        const uint8_t *mask;
+        bool scored;
+        __device__ __forceinline__ double depth(const double R[9], const double t[3], const float *X) const {
+            return R[6] * X[0] + R[7] * X[1] + R[8] * X[2] + t[2];
+        }
+        __device__ __forceinline__ void accumulate_row(const double R[9], const double t[3], const float *X, const float *uv, double acc[NACC]) const {
+            accumulate(R, t, X, uv, cam, acc);
+        }
+    };
+    __device__ __forceinline__ int cameras() const { return 1; }
+    __device__ __forceinline__ Camera camera(int) const { return Camera{corr_, n, cam_, mask_, cam_.fx > 0.f && cam_.fy > 0.f}; }
+};
+
+struct RigCovView {
+    RigOperands rig;
+    int s;
+    const uint8_t *mask_;   // of image 0 of this rig (C x n_max)
+    struct Camera {
+        CorrGlobal corr;
+        int n;
+        Cam cam;
+        const uint8_t *mask;
+        bool scored;
+        const float *e;
+        __device__ __forceinline__ double depth(const double R[9], const double t[3], const float *X) const {   // as accumulate_rig carries the point
+            const double xr = R[0] * X[0] + R[1] * X[1] + R[2] * X[2] + t[0], yr = R[3] * X[0] + R[4] * X[1] + R[5] * X[2] + t[1],
+                         zr = R[6] * X[0] + R[7] * X[1] + R[8] * X[2] + t[2];
+            return (double)e[6] * xr + (double)e[7] * yr + (double)e[8] * zr + (double)e[11];
+        }
+        __device__ __forceinline__ void accumulate_row(const double R[9], const double t[3], const float *X, const float *uv, double acc[NACC]) const {
+            accumulate_rig(R, t, e, X, uv, cam, acc);
+        }
+    };
+    __device__ __forceinline__ int cameras() const { return rig.cameras; }
+    __device__ __forceinline__ Camera camera(int c) const {
+        const int f = s * rig.cameras + c;
+        return Camera{rig.op.corr(f), rig.op.rows(f), rig.op.cam(f), mask_ + (size_t)c * rig.op.n_max, rig.usable(f), rig.E(s, c)};
+    }
+};
+
+__device__ __forceinline__ bool finite_d(double v) { return fabs(v) <= 1.7976931348623157e308; }   // false for NaN and Inf
+
+// One wave, one body.  pose (12) and result (3) are the solver's outputs for the body; sigma_px <= 0: estimate the pixel variance.
+// cov, info (36 each, row-major, exactly symmetric), stat (4) = [ok, n, sigma_hat^2, min_pivot].  ok = 0 writes zeros, never NaN or Inf.
+template <class View>
+__device__ __forceinline__ void covariance_body(const View &view, const float *pose, const int32_t *result, float sigma_px, double *cov,
+                                                double *info, double *stat) {
+    const int lane = threadIdx.x & 63;
+    double acc[NACC];
+    for (int k = 0; k < NACC; ++k) acc[k] = 0.0;
+    double R[9], t[3];
+    for (int k = 0; k < 9; ++k) R[k] = (double)pose[k];
+    for (int k = 0; k < 3; ++k) t[k] = (double)pose[9 + k];
+    const bool solved = result[0] != 0;   // body-uniform
+    bool any_camera = false;
+    int used = 0;
+    if (solved)
+        for (int cc = 0; cc < view.cameras(); ++cc) {
+            const auto cv = view.camera(cc);
+            if (!cv.scored) continue;
+            any_camera = true;
+            for (int i = lane; i < cv.n; i += 64)
+                if (cv.mask[i]) {
+                    float Xi[3], uvi[2];
+                    cv.corr.load(i, Xi, uvi);
+                    if (cv.depth(R, t, Xi) > 1e-6) {   // the solver's inlier rule: a NaN depth compares false
+                        cv.accumulate_row(R, t, Xi, uvi, acc);
+                        ++used;
+                    }
+                }
+        }
+    for (int k = 0; k < NACC; ++k) acc[k] = wave_sum_d(acc[k]);
+    for (int o = 32; o > 0; o >>= 1) used += __shfl_xor(used, o, 64);
+    if (lane != 0) return;
+
+    double H[6][6], C[6][6], I[6][6];
+    {
+        int k = 0;
+        for (int i = 0; i < 6; ++i)
+            for (int j = i; j < 6; ++j) { H[i][j] = acc[k]; H[j][i] = acc[k]; ++k; }
+    }
+    const double cost = acc[27];
+    const int dof = 2 * used - 6;
+    bool ok = solved && any_camera;
+    for (int k = 0; k < NACC; ++k) ok = ok && finite_d(acc[k]);
+    const double sigma_hat2 = (ok && dof > 0) ? cost / (double)dof : 0.0;
+    const double sigma2 = sigma_px > 0.f ? (double)sigma_px * (double)sigma_px : sigma_hat2;
+    ok = ok && (sigma_px > 0.f || dof > 0) && sigma2 > 0.0;
+    double d[6];
+    for (int i = 0; i < 6; ++i) {
+        ok = ok && H[i][i] > 0.0;
+        d[i] = ok ? 1.0 / sqrt(H[i][i]) : 0.0;
+    }
+    // Cholesky of Hs = D^-1/2 H D^-1/2 (unit diagonal), then L^-1: fixed trip counts, a failed pivot only clears `ok`
+    double L[6][6], Li[6][6], min_pivot = 1.0;
+    for (int i = 0; i < 6; ++i)
+        for (int j = 0; j < 6; ++j) { L[i][j] = 0.0; Li[i][j] = 0.0; }
+    for (int j = 0; j < 6; ++j) {
+        double sacc = 1.0;
+        for (int k = 0; k < j; ++k) sacc -= L[j][k] * L[j][k];
+        const bool good = sacc > 1e-12;   // false for NaN
+        ok = ok && good;
+        min_pivot = (good && sacc < min_pivot) ? sacc : min_pivot;
+        const double piv = good ? sqrt(sacc) : 1.0;
+        L[j][j] = piv;
+        for (int i = j + 1; i < 6; ++i) {
+            double v = H[i][j] * d[i] * d[j];
+            for (int k = 0; k < j; ++k) v -= L[i][k] * L[j][k];
+            L[i][j] = v / piv;
+        }
+    }
+    for (int j = 0; j < 6; ++j) {   // column j of L^-1 by forward substitution
+        Li[j][j] = 1.0 / L[j][j];
+        for (int i = j + 1; i < 6; ++i) {
+            double v = 0.0;
+            for (int k = j; k < i; ++k) v -= L[i][k] * Li[k][j];
+            Li[i][j] = v / L[i][i];
+        }
+    }
+    for (int i = 0; i < 6; ++i)
+        for (int j = 0; j <= i; ++j) {   // one triangle, mirrored: Hs^-1 = L^-T L^-1
+            double v = 0.0;
+            for (int k = i; k < 6; ++k) v += Li[k][i] * Li[k][j];
+            const double c = sigma2 * (d[i] * d[j] * v), f = ok ? H[i][j] / sigma2 : 0.0;
+            ok = ok && finite_d(c) && finite_d(f);
+            C[i][j] = c; C[j][i] = c;
+            I[i][j] = f; I[j][i] = f;
+        }
+    for (int i = 0; i < 6; ++i)
+        for (int j = 0; j < 6; ++j) {
+            cov[6 * i + j] = ok ? C[i][j] : 0.0;
+            info[6 * i + j] = ok ? I[i][j] : 0.0;
+        }
+    stat[0] = ok ? 1.0 : 0.0;
+    stat[1] = (double)used;
+    stat[2] = finite_d(sigma_hat2) ? sigma_hat2 : 0.0;
+    stat[3] = ok ? min_pivot : 0.0;
+}
+
+__global__ __launch_bounds__(64) void pose_covariance_kernel(const float *obj, const float *img, const int32_t *count_dev, int n_max, Cam cam,
+                                                             const float *pose, const int32_t *result, const uint8_t *mask, float sigma_px,
+                                                             double *cov, double *info, double *stat) {
+    const int n = count_dev ? min(*count_dev, n_max) : n_max;
+    covariance_body(FrameCovView{CorrGlobal{obj, img, img + 1, 2}, n, cam, mask}, pose, result, sigma_px, cov, info, stat);
+}
+
+// frame f = one wave: pose (frames, 12), result (frames, 3), mask (frames, n_max) -> cov, info (frames, 36), stat (frames, 4)
+__global__ __launch_bounds__(64 * COV_WAVES) void pose_covariance_batch_kernel(BatchOperands op, int frames, const float *pose,
+                                                                               const int32_t *result, const uint8_t *mask, float sigma_px,
+                                                                               double *cov, double *info, double *stat) {
+    const int f = blockIdx.x * COV_WAVES + (threadIdx.x >> 6);
+    if (f >= frames) return;   // wave-uniform; the body has no barrier
+    covariance_body(FrameCovView{op.corr(f), op.rows(f), op.cam(f), mask + (size_t)f * op.n_max}, pose + 12 * f, result + 3 * f, sigma_px,
+                    cov + 36 * (size_t)f, info + 36 * (size_t)f, stat + 4 * (size_t)f);
+}
+
+// rig s = one wave: rig_pose (rigs, 12), rig_result (rigs, 3), mask (rigs C, n_max) -> cov, info (rigs, 36), stat (rigs, 4)
+__global__ __launch_bounds__(64 * COV_WAVES) void pose_covariance_rig_kernel(RigOperands rig, int rigs, const float *rig_pose,
+                                                                             const int32_t *rig_result, const uint8_t *mask, float sigma_px,
+                                                                             double *cov, double *info, double *stat) {
+    const int s = blockIdx.x * COV_WAVES + (threadIdx.x >> 6);
+    if (s >= rigs) return;
+    covariance_body(RigCovView{rig, s, mask + (size_t)s * rig.cameras * rig.op.n_max}, rig_pose + 12 * s, rig_result + 3 * s, sigma_px,
+                    cov + 36 * (size_t)s, info + 36 * (size_t)s, stat + 4 * (size_t)s);
+}
+
 // ---- registration errors of B poses (evaluation/eval_all.py:16-22): P_diff = inv(P_pred) P_gt, RTE = |t|, RRE = sum |euler 'xzy'| in degrees
 // (pose_errors.h: the body, shared with cofi_eval_monitors)
 template <class T>
@@ -780,6 +964,50 @@ __global__ __launch_bounds__(64) void pose_errors_kernel(const float *pose, cons
     const int f = blockIdx.x * 64 + threadIdx.x;
     if (f >= frames) return;
     pose_errors_frame(pose + 12 * f, P_gt + 16 * f, out + 2 * f, out + 2 * f + 1);
+}
+
+// ---- normalised estimation error squared of B poses against ground truth, in the tangent space of the covariance: omega =
+// log(R_gt R_est^T), v = t_gt - exp(omega) t_est, e = (omega, v), nees = e^T info e; NaN where stat[0] == 0.  One thread per body, fp64.
+template <class T>
+__global__ __launch_bounds__(64) void pose_nees_kernel(const float *pose, const T *P_gt, const double *info, const double *stat, int frames,
+                                                       double *out) {
+    const int f = blockIdx.x * 64 + threadIdx.x;
+    if (f >= frames) return;
+    if (stat[4 * (size_t)f] == 0.0) {
+        out[f] = __builtin_nan("");
+        return;
+    }
+    const float *p = pose + 12 * f;
+    const T *G = P_gt + 16 * f;
+    double M[9];   // R_gt R_est^T
+    for (int r = 0; r < 3; ++r)
+        for (int c = 0; c < 3; ++c)
+            M[3 * r + c] = (double)G[4 * r] * (double)p[3 * c] + (double)G[4 * r + 1] * (double)p[3 * c + 1] + (double)G[4 * r + 2] * (double)p[3 * c + 2];
+    const double a[3] = {0.5 * (M[7] - M[5]), 0.5 * (M[2] - M[6]), 0.5 * (M[3] - M[1])};   // sin(theta) times the axis
+    const double sn = sqrt(a[0] * a[0] + a[1] * a[1] + a[2] * a[2]), cs = 0.5 * (M[0] + M[4] + M[8] - 1.0);
+    const double th = atan2(sn, cs), scale = sn > 1e-12 ? th / sn : 1.0;
+    double e[6];
+    for (int k = 0; k < 3; ++k) e[k] = a[k] * scale;
+    // exp(omega) by Rodrigues, as the refit builds it
+    const double wx = e[0], wy = e[1], wz = e[2];
+    const double W[9] = {0, -wz, wy, wz, 0, -wx, -wy, wx, 0};
+    double W2[9];
+    for (int r = 0; r < 3; ++r)
+        for (int c = 0; c < 3; ++c) W2[3 * r + c] = W[3 * r] * W[c] + W[3 * r + 1] * W[3 + c] + W[3 * r + 2] * W[6 + c];
+    const double ka = th < 1e-12 ? 1.0 : sin(th) / th, kb = th < 1e-12 ? 0.0 : (1.0 - cos(th)) / (th * th);
+    for (int r = 0; r < 3; ++r) {
+        double Er[3];
+        for (int c = 0; c < 3; ++c) Er[c] = ((r == c) ? 1.0 : 0.0) + ka * W[3 * r + c] + kb * W2[3 * r + c];
+        e[3 + r] = (double)G[4 * r + 3] - (Er[0] * (double)p[9] + Er[1] * (double)p[10] + Er[2] * (double)p[11]);
+    }
+    const double *A = info + 36 * (size_t)f;
+    double q = 0.0;
+    for (int i = 0; i < 6; ++i) {
+        double row = 0.0;
+        for (int j = 0; j < 6; ++j) row += A[6 * i + j] * e[j];
+        q += e[i] * row;
+    }
+    out[f] = q;
 }
 
 }  // namespace
@@ -878,5 +1106,57 @@ extern "C" int cofi_pose_errors(const float *pose, const void *P_gt, int gt_is_f
         hipLaunchKernelGGL(pose_errors_kernel<double>, dim3(cofi_cdiv(frames, 64)), dim3(64), 0, s, pose, (const double *)P_gt, frames, out);
     else
         hipLaunchKernelGGL(pose_errors_kernel<float>, dim3(cofi_cdiv(frames, 64)), dim3(64), 0, s, pose, (const float *)P_gt, frames, out);
+    return cofi_launch_status();
+}
+
+extern "C" int cofi_pose_covariance(const float *obj, const float *img, const int32_t *count_dev, int n_max, float fx, float fy, float cx,
+                                    float cy, const float *pose, const int32_t *result, const uint8_t *inlier_mask, float sigma_px, double *cov,
+                                    double *info, double *stat, cofi_stream_t stream) {
+    if (!obj || !img || !pose || !result || !inlier_mask || !cov || !info || !stat || n_max <= 0 || !(fx > 0.f) || !(fy > 0.f) ||
+        !(sigma_px == sigma_px))
+        return COFI_EINVAL;
+    hipLaunchKernelGGL(pose_covariance_kernel, dim3(1), dim3(64), 0, cofi_s(stream), obj, img, count_dev, n_max, Cam{fx, fy, cx, cy}, pose, result,
+                       inlier_mask, sigma_px, cov, info, stat);
+    return cofi_launch_status();
+}
+
+extern "C" int cofi_pose_covariance_batch(const float *obj, int obj_frame_stride, const float *img, int img_frame_stride, int coord_major,
+                                          const int32_t *count_dev, int count_stride, const float *K_dev, int n_max, int frames,
+                                          const float *pose, const int32_t *result, const uint8_t *inlier_mask, float sigma_px, double *cov,
+                                          double *info, double *stat, cofi_stream_t stream) {
+    if (!obj || !img || !K_dev || !pose || !result || !inlier_mask || !cov || !info || !stat || n_max <= 0 || frames <= 0 || frames > 65535 ||
+        obj_frame_stride < 3 * n_max || img_frame_stride < 2 * n_max || (count_dev && count_stride < 1) || !(sigma_px == sigma_px))
+        return COFI_EINVAL;
+    const BatchOperands op{obj, img, count_dev, K_dev, obj_frame_stride, img_frame_stride, count_stride, coord_major ? 1 : 0, n_max};
+    hipLaunchKernelGGL(pose_covariance_batch_kernel, dim3(cofi_cdiv(frames, COV_WAVES)), dim3(64 * COV_WAVES), 0, cofi_s(stream), op, frames, pose,
+                       result, inlier_mask, sigma_px, cov, info, stat);
+    return cofi_launch_status();
+}
+
+extern "C" int cofi_pose_covariance_rig(const float *obj, int obj_frame_stride, const float *img, int img_frame_stride, int coord_major,
+                                        const int32_t *count_dev, int count_stride, const float *K_dev, const float *ext_dev, int ext_rig_stride,
+                                        int n_max, int cameras, int rigs, const float *rig_pose, const int32_t *rig_result,
+                                        const uint8_t *inlier_mask, float sigma_px, double *cov, double *info, double *stat,
+                                        cofi_stream_t stream) {
+    if (!obj || !img || !K_dev || !ext_dev || !rig_pose || !rig_result || !inlier_mask || !cov || !info || !stat || n_max <= 0 || cameras <= 0 ||
+        rigs <= 0 || (long long)rigs * cameras > 65535 || obj_frame_stride < 3 * n_max || img_frame_stride < 2 * n_max ||
+        (count_dev && count_stride < 1) || (ext_rig_stride != 0 && ext_rig_stride < 12 * cameras) || !(sigma_px == sigma_px))
+        return COFI_EINVAL;
+    const RigOperands rig{BatchOperands{obj, img, count_dev, K_dev, obj_frame_stride, img_frame_stride, count_stride, coord_major ? 1 : 0, n_max},
+                          ext_dev, ext_rig_stride, cameras};
+    hipLaunchKernelGGL(pose_covariance_rig_kernel, dim3(cofi_cdiv(rigs, COV_WAVES)), dim3(64 * COV_WAVES), 0, cofi_s(stream), rig, rigs, rig_pose,
+                       rig_result, inlier_mask, sigma_px, cov, info, stat);
+    return cofi_launch_status();
+}
+
+extern "C" int cofi_pose_nees(const float *pose, const void *P_gt, int gt_is_f64, const double *info, const double *stat, int frames,
+                              double *nees, cofi_stream_t stream) {
+    if (!pose || !P_gt || !info || !stat || !nees || frames <= 0) return COFI_EINVAL;
+    hipStream_t s = cofi_s(stream);
+    if (gt_is_f64)
+        hipLaunchKernelGGL(pose_nees_kernel<double>, dim3(cofi_cdiv(frames, 64)), dim3(64), 0, s, pose, (const double *)P_gt, info, stat, frames,
+                           nees);
+    else
+        hipLaunchKernelGGL(pose_nees_kernel<float>, dim3(cofi_cdiv(frames, 64)), dim3(64), 0, s, pose, (const float *)P_gt, info, stat, frames, nees);
     return cofi_launch_status();
 }

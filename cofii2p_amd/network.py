@@ -496,7 +496,8 @@ class CoFiI2P(nn.Module):
 
     @torch.no_grad()
     def forward_async(self, slot: int, pc_data_dict, img, mode: str = "test", inputs_stable: bool = False, pose_K=None,
-                      pose_iterations: int = 10000, pose_seed: int = 0, eval_into=None, cameras: int = 1, rig_extrinsics=None, fuse_into=None):
+                      pose_iterations: int = 10000, pose_seed: int = 0, eval_into=None, cameras: int = 1, rig_extrinsics=None, fuse_into=None,
+                      pose_cov=False):
         """Enqueue one test-mode forward on the CURRENT stream through the hipGraph of slot `slot` and return
         immediately (no host sync).  `img` (1,3,H,W) = one frame, or (B,3,H,W) with a stack-mode `pc_data_dict`
         (see stack_frames) = B frames through the same launches.  Slots own their static buffers and scratch, so
@@ -544,7 +545,23 @@ class CoFiI2P(nn.Module):
         (`points[0]`: S = B // cameras clouds of N rows), its images, the per-image poses and results of handle["pose"], and pose_K with
         k_scale = image width / fine-map width (pose_K belongs to the fine map the matches live on).  handle["fusion"] = buffers.  Refused
         before anything is enqueued: fuse_into without pose_K, buffers that were not made for (S, N, B, H, W, 3) on the device of the
-        images.  With the default None nothing about the call, its handle or its launches changes."""
+        images.  With the default None nothing about the call, its handle or its launches changes.
+
+        pose_cov=True, or the 1-sigma pixel noise as a number (needs pose_K): the 6 x 6 covariance of every pose (pose.pose_covariance_batch:
+        one launch behind the pose tail, on the same stream, before the handle's `done` event).  handle["pose"] gains "cov" (B,6,6), "info"
+        (B,6,6) and "cov_stat" (B,4) float64, owned by the slot like the poses.  With rig_extrinsics handle["rig_pose"] gains the same three
+        entries, (S, ...), from pose.pose_covariance_rig in the rig's tangent space, and the per-image entries are the frame form at E_c o rig
+        pose on that image's own rows.  True estimates the pixel variance from the residuals.  Refused before anything is enqueued:
+        pose_cov without pose_K, a pixel noise that is not a finite number > 0.  With the default False nothing about the call, its handle,
+        its buffers or its launches changes."""
+        if pose_cov is not False and pose_cov is not None:
+            from . import pose as _pose
+
+            if pose_K is None:
+                raise _lib.CofiError("forward_async(pose_cov=...): the covariance belongs to the pose tail - pass pose_K")
+            pose_cov = (_pose._sigma(pose_cov) or None,)   # (None,): estimate the pixel variance
+        else:
+            pose_cov = None
         if mode != "test":
             if cameras != 1:
                 raise ValueError("a rig (cameras = %d > 1) serves mode='test' only, got mode=%r" % (cameras, mode))
@@ -584,7 +601,7 @@ class CoFiI2P(nn.Module):
                                      % (want, img.device))
         with ops.arithmetic(self.arithmetic):
             return self._forward_async(slot, pc_data_dict, img, mode, inputs_stable, pose_K, pose_iterations, pose_seed, eval_into, cameras,
-                                       rig_extrinsics, fuse_into)
+                                       rig_extrinsics, fuse_into, pose_cov)
 
     @staticmethod
     def _check_rig(pc_data_dict, img, cameras):
@@ -604,9 +621,20 @@ class CoFiI2P(nn.Module):
                 raise _lib.CofiError("forward_async: B = %d images with C = %d cameras are S = %d clouds, which does not divide the %d rows of %s"
                                      % (B, cameras, S, t.shape[0], name))
 
-    def _enqueue_pose(self, slot, outs, K, iterations, seed, cameras=1, rig_ext=None):
-        """the batched pose tail of a submission (with rig_ext = (ext, rig stride): the rig solve), on the current stream, into buffers
-        the slot owns -> (handle["pose"], K on the device, handle["rig_pose"] or None)"""
+    @staticmethod
+    def _cov_bufs(holder, frames, dev):
+        """the covariance buffers a slot owns for `frames` bodies, made when a submission first asks for them"""
+        c = holder.get("cov")
+        if c is None:
+            c = holder["cov"] = {"cov": torch.empty((frames, 6, 6), dtype=torch.float64, device=dev),
+                                 "info": torch.empty((frames, 6, 6), dtype=torch.float64, device=dev),
+                                 "stat": torch.empty((frames, 4), dtype=torch.float64, device=dev)}
+        return c
+
+    def _enqueue_pose(self, slot, outs, K, iterations, seed, cameras=1, rig_ext=None, pose_cov=None):
+        """the batched pose tail of a submission (with rig_ext = (ext, rig stride): the rig solve; with pose_cov = (sigma_px or None,): the
+        covariance launch behind it), on the current stream, into buffers the slot owns -> (handle["pose"], K on the device,
+        handle["rig_pose"] or None)"""
         from . import pose as _pose
 
         if "coarse_pts_all" not in outs[0]:
@@ -646,13 +674,28 @@ class CoFiI2P(nn.Module):
                 ext = buf
             rig, per = _pose.solve_pnp_ransac_rig_into(cpts, fxy, K, (ext, estride), cameras, cnt[:, 0], r["ws"], r["pose"], r["result"],
                                                        b["pose"], b["result"], b["mask"], iterations=iterations, seed=seed, coord_major=True)
+            if pose_cov is not None:
+                c = self._cov_bufs(r, S, dev)
+                _pose.pose_covariance_rig_into(cpts, fxy, K, (ext, estride), cameras, cnt[:, 0], r["pose"], r["result"], b["mask"], c["cov"],
+                                               c["info"], c["stat"], sigma_px=pose_cov[0], coord_major=True)
+                rig.update(cov=c["cov"], info=c["info"], cov_stat=c["stat"])
+                c = self._cov_bufs(b, B, dev)   # per image: the frame form at E_c o rig pose on the image's own rows
+                _pose.pose_covariance_batch_into(cpts, fxy, K, cnt[:, 0], b["pose"], b["result"], b["mask"], c["cov"], c["info"], c["stat"],
+                                                 sigma_px=pose_cov[0], coord_major=True)
+                per.update(cov=c["cov"], info=c["info"], cov_stat=c["stat"])
             return per, K, rig
         res, R, t, mask = _pose.solve_pnp_ransac_batch_into(cpts, fxy, K, cnt[:, 0], b["ws"], b["pose"], b["result"], b["mask"],
                                                             iterations=iterations, seed=seed, coord_major=True)
-        return {"result": res, "R": R, "t": t, "inliers": mask}, K, None
+        pose = {"result": res, "R": R, "t": t, "inliers": mask}
+        if pose_cov is not None:
+            c = self._cov_bufs(b, B, dev)
+            _pose.pose_covariance_batch_into(cpts, fxy, K, cnt[:, 0], b["pose"], b["result"], b["mask"], c["cov"], c["info"], c["stat"],
+                                             sigma_px=pose_cov[0], coord_major=True)
+            pose.update(cov=c["cov"], info=c["info"], cov_stat=c["stat"])
+        return pose, K, None
 
     def _forward_async(self, slot, pc_data_dict, img, mode, inputs_stable, pose_K=None, pose_iterations=10000, pose_seed=0, eval_into=None,
-                       cameras=1, rig_ext=None, fuse_into=None):
+                       cameras=1, rig_ext=None, fuse_into=None, pose_cov=None):
         P = self._pack(img.device)
         if inputs_stable:
             for k in ("points", "neighbors", "subsampling", "upsampling"):
@@ -675,7 +718,7 @@ class CoFiI2P(nn.Module):
             host = hosts[(slot, len(outs))] = torch.empty((len(outs), 2), dtype=torch.int32, pin_memory=True)
         host.copy_(outs[0]["count_all"], non_blocking=True)
         pose, K_dev, rig_pose = (None, None, None) if pose_K is None else self._enqueue_pose(slot, outs, pose_K, pose_iterations, pose_seed,
-                                                                                             cameras, rig_ext)
+                                                                                             cameras, rig_ext, pose_cov)
         if eval_into is not None:   # the evaluation monitors of the submission: one launch behind the pose tail
             from . import evaluation
 

@@ -293,6 +293,206 @@ def pose_errors(pose, P_gt) -> torch.Tensor:
     return out
 
 
+# ---------------------------------------------------------------------------------------------------- pose uncertainty
+# The 6 x 6 Gauss-Newton covariance of the refit's least-squares problem at the pose the solver returned, over the consensus set it wrote
+# into the masks (cofi_pose_covariance*; DESIGN.md, "Pose uncertainty").  Tangent vector (omega, v), rotation first, of the left-multiplied
+# perturbation R' = exp(omega) R, t' = exp(omega) t + v.  cov, info (.., 6, 6) float64, exactly symmetric; stat (.., 4) float64 =
+# [ok, rows used, sigma_hat^2, min_pivot]; ok = 0 goes with all-zero matrices.  NOT a model of outliers inside the gate or of the choice of
+# the consensus set.
+def _sigma(sigma_px) -> float:
+    """None / True: estimate the pixel variance (0 for the kernel); a number: the given 1-sigma pixel noise"""
+    if sigma_px is None or sigma_px is True:
+        return 0.0
+    s = float(sigma_px)
+    if not (s > 0.0 and np.isfinite(s)):
+        raise _lib.CofiError("pose covariance: sigma_px must be a finite number > 0 (or None to estimate it), got %r" % (sigma_px,))
+    return s
+
+
+def _pose12(pose, frames, what):
+    """(R (F,3,3), t (F,3)) or (F,12) -> a contiguous (F,12) float32 buffer; views of one buffer, as the solvers return them, are not copied"""
+    if isinstance(pose, (tuple, list)):
+        R, t = pose
+        if not (torch.is_tensor(R) and torch.is_tensor(t) and tuple(R.shape) == (frames, 3, 3) and tuple(t.shape) == (frames, 3)):
+            raise _lib.CofiError("%s: (R, t) must be (%d,3,3) and (%d,3) tensors" % (what, frames, frames))
+        base = R._base if R._base is not None else None
+        if (base is not None and base is t._base and tuple(base.shape) == (frames, 12) and base.is_contiguous() and R.data_ptr() == base.data_ptr()
+                and t.data_ptr() == base.data_ptr() + 36):
+            pose = base
+        else:
+            pose = torch.cat([R.reshape(frames, 9), t], 1)
+    if not (torch.is_tensor(pose) and pose.is_cuda and pose.dtype == torch.float32 and tuple(pose.shape) == (frames, 12) and pose.is_contiguous()):
+        raise _lib.CofiError("%s: pose must be a contiguous CUDA float32 (%d,12) tensor or a pair (R, t)" % (what, frames))
+    return pose
+
+
+def _cov_buffers(frames, cov, info, stat, dev, what):
+    for t_, shape in ((cov, (frames, 6, 6)), (info, (frames, 6, 6)), (stat, (frames, 4))):
+        if not (torch.is_tensor(t_) and t_.is_cuda and t_.device == dev and t_.dtype == torch.float64 and tuple(t_.shape) == shape
+                and t_.is_contiguous()):
+            raise _lib.CofiError("%s: output buffers must be contiguous CUDA float64 tensors cov (F,6,6), info (F,6,6), stat (F,4) with F = %d"
+                                 % (what, frames))
+
+
+def _solver_outputs(result, mask, frames, images, cap, dev, what):
+    if not (torch.is_tensor(result) and result.is_cuda and result.device == dev and result.dtype == torch.int32
+            and tuple(result.shape) == (frames, 3) and result.is_contiguous()):
+        raise _lib.CofiError("%s: result must be the solver's contiguous CUDA int32 (%d,3) tensor" % (what, frames))
+    if not (torch.is_tensor(mask) and mask.is_cuda and mask.device == dev and mask.dtype == torch.uint8 and tuple(mask.shape) == (images, cap)
+            and mask.is_contiguous()):
+        raise _lib.CofiError("%s: inlier_mask must be the solver's contiguous CUDA uint8 (%d,%d) tensor" % (what, images, cap))
+
+
+def pose_covariance(object_points: torch.Tensor, image_points: torch.Tensor, K, pose, result: torch.Tensor, inlier_mask: torch.Tensor,
+                    sigma_px=None, count: Optional[torch.Tensor] = None):
+    """The covariance of ONE frame's pose (cofi_pose_covariance): the operands of solve_pnp_ransac, then what it returned - pose (12,) or
+    (R, t), result (3,), inlier_mask (n,).  sigma_px: the 1-sigma pixel noise, None to estimate it from the residuals.
+    Returns (cov (6,6), info (6,6), stat (4,)) float64 device tensors."""
+    lib = _lib.load()
+    what = "pose_covariance"
+    for t_, name, w in ((object_points, "object_points", 3), (image_points, "image_points", 2)):
+        if not (torch.is_tensor(t_) and t_.is_cuda and t_.dtype == torch.float32 and t_.dim() == 2 and t_.shape[1] == w and t_.is_contiguous()):
+            raise _lib.CofiError("%s: %s must be a contiguous CUDA float32 (n,%d) tensor" % (what, name, w))
+    n = object_points.shape[0]
+    if image_points.shape[0] != n or n == 0:
+        raise _lib.CofiError("%s: need n >= 1 correspondences of equal count" % what)
+    dev = object_points.device
+    if isinstance(pose, (tuple, list)):
+        pose = (pose[0][None], pose[1][None])
+    else:
+        pose = pose.reshape(1, 12) if torch.is_tensor(pose) else pose
+    pose = _pose12(pose, 1, what)
+    _solver_outputs(result.reshape(1, 3) if torch.is_tensor(result) else result, inlier_mask[None] if torch.is_tensor(inlier_mask) else inlier_mask,
+                    1, 1, n, dev, what)
+    Kh = K.detach().cpu().numpy() if torch.is_tensor(K) else np.asarray(K)
+    cov = torch.empty((6, 6), dtype=torch.float64, device=dev)
+    info = torch.empty((6, 6), dtype=torch.float64, device=dev)
+    stat = torch.empty(4, dtype=torch.float64, device=dev)
+    rc = lib.cofi_pose_covariance(ops._p(object_points), ops._p(image_points), ops._p(count), n, float(Kh[0, 0]), float(Kh[1, 1]), float(Kh[0, 2]),
+                                  float(Kh[1, 2]), ops._p(pose), ops._p(result), ops._p(inlier_mask), _sigma(sigma_px), ops._p(cov), ops._p(info),
+                                  ops._p(stat), ops._stream())
+    _lib.check(rc, "cofi_pose_covariance")
+    return cov, info, stat
+
+
+def pose_covariance_batch_into(object_points, image_points, K, count, pose, result, inlier_mask, cov, info, stat, sigma_px=None,
+                               coord_major: bool = False):
+    """pose_covariance_batch into caller-owned buffers (cov, info (B,6,6), stat (B,4) float64).  Enqueues one kernel on the current stream;
+    nothing else."""
+    lib = _lib.load()
+    what = "pose_covariance_batch"
+    B, cap, K, count, cstride = _batch_operands(object_points, image_points, K, count, coord_major, what)
+    dev = object_points.device
+    pose = _pose12(pose, B, what)
+    _solver_outputs(result, inlier_mask, B, B, cap, dev, what)
+    _cov_buffers(B, cov, info, stat, dev, what)
+    rc = lib.cofi_pose_covariance_batch(ops._p(object_points), 3 * cap, ops._p(image_points), 2 * cap, 1 if coord_major else 0, ops._p(count),
+                                        cstride, ops._p(K), cap, B, ops._p(pose), ops._p(result), ops._p(inlier_mask), _sigma(sigma_px),
+                                        ops._p(cov), ops._p(info), ops._p(stat), ops._stream())
+    _lib.check(rc, "cofi_pose_covariance_batch")
+    return cov, info, stat
+
+
+def pose_covariance_batch(object_points: torch.Tensor, image_points: torch.Tensor, K, pose, result: torch.Tensor, inlier_mask: torch.Tensor,
+                          sigma_px=None, count: Optional[torch.Tensor] = None, coord_major: bool = False):
+    """The covariance of every frame's pose in one launch (cofi_pose_covariance_batch): the operands of solve_pnp_ransac_batch, then what
+    it returned - pose (B,12) or (R (B,3,3), t (B,3)), result (B,3), inlier_mask (B,cap).  Frame f is bit-identical to pose_covariance on
+    its slice.  Returns (cov (B,6,6), info (B,6,6), stat (B,4)) float64 device tensors; no host synchronisation."""
+    B, _, _, _, _ = _batch_operands(object_points, image_points, K, count, coord_major, "pose_covariance_batch")
+    dev = object_points.device
+    cov = torch.empty((B, 6, 6), dtype=torch.float64, device=dev)
+    info = torch.empty((B, 6, 6), dtype=torch.float64, device=dev)
+    stat = torch.empty((B, 4), dtype=torch.float64, device=dev)
+    return pose_covariance_batch_into(object_points, image_points, K, count, pose, result, inlier_mask, cov, info, stat, sigma_px, coord_major)
+
+
+def pose_covariance_rig_into(object_points, image_points, K, extrinsics, cameras, count, rig_pose, rig_result, inlier_mask, cov, info, stat,
+                             sigma_px=None, coord_major: bool = False):
+    """pose_covariance_rig into caller-owned buffers (cov, info (S,6,6), stat (S,4) float64).  extrinsics: what solve_pnp_ransac_rig takes,
+    or the pair rig_extrinsics returned (nothing is converted then).  Enqueues one kernel on the current stream; nothing else."""
+    lib = _lib.load()
+    what = "pose_covariance_rig"
+    B, cap, S, K, count, cstride, ext, estride = _rig_operands(object_points, image_points, K, extrinsics, cameras, count, coord_major, what)
+    dev = object_points.device
+    rig_pose = _pose12(rig_pose, S, what)
+    _solver_outputs(rig_result, inlier_mask, S, B, cap, dev, what)
+    _cov_buffers(S, cov, info, stat, dev, what)
+    rc = lib.cofi_pose_covariance_rig(ops._p(object_points), 3 * cap, ops._p(image_points), 2 * cap, 1 if coord_major else 0, ops._p(count),
+                                      cstride, ops._p(K), ops._p(ext), int(estride), cap, int(cameras), S, ops._p(rig_pose), ops._p(rig_result),
+                                      ops._p(inlier_mask), _sigma(sigma_px), ops._p(cov), ops._p(info), ops._p(stat), ops._stream())
+    _lib.check(rc, "cofi_pose_covariance_rig")
+    return cov, info, stat
+
+
+def pose_covariance_rig(object_points: torch.Tensor, image_points: torch.Tensor, K, extrinsics, cameras: int, rig_pose,
+                        rig_result: torch.Tensor, inlier_mask: torch.Tensor, sigma_px=None, count: Optional[torch.Tensor] = None,
+                        coord_major: bool = False):
+    """ONE covariance per rig, in the rig's tangent space (cofi_pose_covariance_rig): the operands of solve_pnp_ransac_rig, then what it
+    returned - the rig's pose (S,12) or (R, t) and result (S,3), and the per-image inlier masks (B,cap).  The covariance of camera c's own
+    pose follows with transport_covariance(cov, E_c).  Returns (cov (S,6,6), info (S,6,6), stat (S,4)) float64 device tensors."""
+    B, _, S, K, count, _, ext, estride = _rig_operands(object_points, image_points, K, extrinsics, cameras, count, coord_major,
+                                                       "pose_covariance_rig")
+    dev = object_points.device
+    cov = torch.empty((S, 6, 6), dtype=torch.float64, device=dev)
+    info = torch.empty((S, 6, 6), dtype=torch.float64, device=dev)
+    stat = torch.empty((S, 4), dtype=torch.float64, device=dev)
+    return pose_covariance_rig_into(object_points, image_points, K, (ext, estride), cameras, count, rig_pose, rig_result, inlier_mask, cov, info,
+                                    stat, sigma_px, coord_major)
+
+
+def pose_nees(pose, P_gt, info: torch.Tensor, stat: torch.Tensor) -> torch.Tensor:
+    """Normalised estimation error squared of B poses against ground truth (cofi_pose_nees): e = (log(R_gt R_est^T), t_gt - exp(omega)
+    t_est), nees = e^T info e - chi-square with 6 degrees of freedom for a calibrated covariance; NaN where stat[:, 0] == 0.  pose (B,12)
+    or (R, t); P_gt (B,4,4) float64 or float32 in the direction of the pose, as pose_errors takes it; info (B,6,6), stat (B,4) of
+    pose_covariance*.  Returns a (B,) float64 device tensor; nothing is synchronised."""
+    lib = _lib.load()
+    what = "pose_nees"
+    if not (torch.is_tensor(info) and info.is_cuda and info.dtype == torch.float64 and info.dim() == 3 and tuple(info.shape[1:]) == (6, 6)
+            and info.is_contiguous() and info.shape[0] >= 1):
+        raise _lib.CofiError("%s: info must be a contiguous CUDA float64 (B,6,6) tensor with B >= 1" % what)
+    B, dev = info.shape[0], info.device
+    if not (torch.is_tensor(stat) and stat.is_cuda and stat.device == dev and stat.dtype == torch.float64 and tuple(stat.shape) == (B, 4)
+            and stat.is_contiguous()):
+        raise _lib.CofiError("%s: stat must be a contiguous CUDA float64 (%d,4) tensor" % (what, B))
+    pose = _pose12(pose, B, what)
+    if not torch.is_tensor(P_gt):
+        P_gt = torch.as_tensor(np.asarray(P_gt))
+    if tuple(P_gt.shape) != (B, 4, 4) or P_gt.dtype not in (torch.float64, torch.float32):
+        raise _lib.CofiError("%s: P_gt must be a (%d,4,4) float64 or float32 tensor" % (what, B))
+    P_gt = P_gt.to(dev, non_blocking=True).contiguous()
+    out = torch.empty(B, dtype=torch.float64, device=dev)
+    _lib.check(lib.cofi_pose_nees(ops._p(pose), ops._p(P_gt), 1 if P_gt.dtype == torch.float64 else 0, ops._p(info), ops._p(stat), B, ops._p(out),
+                                  ops._stream()), "cofi_pose_nees")
+    return out
+
+
+def _skew(t):
+    z = torch.zeros((), dtype=t.dtype, device=t.device)
+    return torch.stack([torch.stack([z, -t[2], t[1]]), torch.stack([t[2], z, -t[0]]), torch.stack([-t[1], t[0], z])])
+
+
+def transport_covariance(cov: torch.Tensor, E) -> torch.Tensor:
+    """The covariance of a camera's pose E_c o T from the rig's (float64 torch): a perturbation (omega, v) of T perturbs E_c o T by
+    (R_c omega, [t_c]x R_c omega + R_c v), so Sigma_c = A Sigma A^T with A = [[R_c, 0], [[t_c]x R_c, R_c]].  cov (6,6) or (S,6,6); E (3,4) /
+    (4,4), camera <- rig, tensor or array."""
+    cov = torch.as_tensor(cov).to(torch.float64)
+    E = torch.as_tensor(np.asarray(E, dtype=np.float64) if not torch.is_tensor(E) else E).to(device=cov.device, dtype=torch.float64)
+    if tuple(cov.shape[-2:]) != (6, 6) or tuple(E.shape) not in ((3, 4), (4, 4)):
+        raise _lib.CofiError("transport_covariance: cov (..,6,6) and E (3,4) or (4,4), got %s and %s" % (tuple(cov.shape), tuple(E.shape)))
+    Rc, tc = E[:3, :3], E[:3, 3]
+    A = torch.zeros((6, 6), dtype=torch.float64, device=cov.device)
+    A[:3, :3], A[3:, 3:], A[3:, :3] = Rc, Rc, _skew(tc) @ Rc
+    out = A @ cov @ A.T
+    return 0.5 * (out + out.transpose(-1, -2))
+
+
+def covariance_sigmas(cov: torch.Tensor):
+    """(rotation 1-sigma in degrees = sqrt(trace(Sigma_omega omega)) 180 / pi, translation 1-sigma in the units of the cloud =
+    sqrt(trace(Sigma_vv))) of a covariance (6,6) or (..,6,6)"""
+    d = torch.diagonal(torch.as_tensor(cov).to(torch.float64), dim1=-2, dim2=-1)
+    return torch.sqrt(d[..., :3].sum(-1)) * (180.0 / np.pi), torch.sqrt(d[..., 3:].sum(-1))
+
+
 def euler_xzy_deg(Rm: np.ndarray) -> np.ndarray:
     """scipy's Rotation.from_matrix(Rm).as_euler('xzy', degrees=True) (eval_all.py:20-21) without scipy: R = Ry(c) Rz(b) Rx(a)."""
     b = np.arcsin(np.clip(Rm[1, 0], -1.0, 1.0))

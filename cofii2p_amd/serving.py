@@ -41,6 +41,11 @@ Registered clouds (`fusion.fuse_into` behind the pose tail of every stack): `Fra
 rig_extrinsics=E])`; `fusion_result(t)` -> {"depth" (H,W), "index" (H,W), "flags" (N,), "stats" (4,)} of the ticket's image plus "color"
 (N,3) and "camera" (N,) of its cloud - with cameras = C the maps of all C images of the ticket's rig, (C,H,W) / (C,N) / (C,4).  One
 `fusion.FusionBuffers` per stack of the ring, so the views live as long as `result(t)` does.
+
+Pose uncertainty (`pose.pose_covariance_batch` / `pose_covariance_rig` behind the pose tail of every stack): `FrameBatcher(model, pose=True,
+covariance=True[, sigma_px=...])`; `covariance_result(t)` -> (cov (6,6), info (6,6), stat (4,) = [ok, rows used, sigma_hat^2, min_pivot])
+float64 of the pose of the ticket's image, `rig_covariance_result(t)` -> the same of its rig (with rig_extrinsics), in the tangent space
+(omega, v) of the left-multiplied perturbation.  sigma_px: the 1-sigma pixel noise if it is known; None estimates it from the residuals.
 """
 from typing import Dict, List, Optional, Tuple
 
@@ -53,9 +58,17 @@ from .preprocess import FrameStack
 class FrameBatcher:
     def __init__(self, model: CoFiI2P, batch: int = 16, streams: int = 4, ring: Optional[int] = None, slot_base: int = 200,
                  pose: bool = False, pose_iterations: int = 10000, eval_table=None, cameras: int = 1, rig_extrinsics=None,
-                 fuse: bool = False):
+                 fuse: bool = False, covariance: bool = False, sigma_px: Optional[float] = None):
         if batch < 1:
             raise ValueError("batch must be >= 1")
+        if covariance and not pose:
+            raise ValueError("FrameBatcher(covariance=True): the covariance belongs to the poses - pass pose=True")
+        if sigma_px is not None and not covariance:
+            raise ValueError("FrameBatcher(sigma_px=...): the pixel noise goes with covariance=True")
+        if sigma_px is not None and not (float(sigma_px) > 0.0 and float(sigma_px) < float("inf")):
+            raise ValueError("FrameBatcher(sigma_px=...): a finite number > 0, or None to estimate the pixel variance")
+        self.covariance = bool(covariance)
+        self._pose_cov = {} if not covariance else {"pose_cov": True if sigma_px is None else float(sigma_px)}
         if fuse and not pose:
             raise ValueError("FrameBatcher(fuse=True): the fusion reads the poses - pass pose=True")
         if cameras < 1 or batch % cameras:
@@ -140,6 +153,7 @@ class FrameBatcher:
                 self._fusion[j] = fusion.FusionBuffers(clouds, st.pyr["points"][0].shape[0] // clouds, self.B, st.img.shape[2], st.img.shape[3],
                                                        st.img.shape[1], st.img.device)
             rig["fuse_into"] = self._fusion[j]
+        rig.update(self._pose_cov)
         with torch.cuda.stream(self._stream(j)):
             if self.eval_table is not None:
                 self._handles[j] = self.model.forward_async(self.slot_base + j, st.pyr, st.img, inputs_stable=True, pose_K=self._K[j],
@@ -370,6 +384,24 @@ class FrameBatcher:
         r = self._rig_poses[ticket[0]]
         s = ticket[2] // self.C
         return r["result"][s], r["R"][s], r["t"][s]
+
+    def covariance_result(self, ticket: Tuple[int, int, int]):
+        """-> (cov (6,6), info (6,6), stat (4,) = [ok, rows used, sigma_hat^2, min_pivot]) float64 of the pose of the ticket's image
+        (pose.pose_covariance_batch behind the stack's pose tail).  Device views of the slot's buffers, same lifetime as `result(ticket)`."""
+        if not self.covariance:
+            raise RuntimeError("FrameBatcher: built without covariance=True")
+        self.pose_result(ticket)   # the ticket checks, the flush and the collection
+        p, f = self._poses[ticket[0]], ticket[2]
+        return p["cov"][f], p["info"][f], p["cov_stat"][f]
+
+    def rig_covariance_result(self, ticket: Tuple[int, int, int]):
+        """-> (cov (6,6), info (6,6), stat (4,)) of the pose of the ticket's RIG, in the rig's tangent space (pose.pose_covariance_rig): the
+        same for the C tickets of a rig.  Same lifetime as `result(ticket)`."""
+        if not self.covariance:
+            raise RuntimeError("FrameBatcher: built without covariance=True")
+        self.rig_pose_result(ticket)   # refuses a batcher without rig_extrinsics
+        r, s = self._rig_poses[ticket[0]], ticket[2] // self.C
+        return r["cov"][s], r["info"][s], r["cov_stat"][s]
 
     def fusion_result(self, ticket: Tuple[int, int, int]) -> Dict[str, torch.Tensor]:
         """-> the registered cloud of the ticket's frame: {"depth" (H,W) float32, "index" (H,W) int32, "flags" (N,) uint8, "stats" (4,) int32}

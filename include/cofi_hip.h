@@ -705,6 +705,45 @@ int cofi_pnp_ransac_rig(const float *obj, int obj_frame_stride, const float *img
  * out (frames, 2) float64 = [RTE = |t(P_diff)|, RRE = sum |euler 'xzy' of R(P_diff)| in degrees, scipy's gimbal convention].
  * pose (frames, 12) as cofi_pnp_ransac writes it; P_gt (frames, 4, 4) row-major, float64 if gt_is_f64 != 0, else float32. */
 int cofi_pose_errors(const float *pose, const void *P_gt, int gt_is_f64, int frames, double *out, cofi_stream_t stream);
+/* Pose uncertainty: the 6 x 6 Gauss-Newton covariance of the refit's least-squares problem at the pose cofi_pnp_ransac returned, over
+ * the consensus set it wrote into inlier_mask.  obj, img, count_dev, n_max and the intrinsics are that call's operands; pose (12),
+ * result (3) and inlier_mask (n_max) its outputs, read only.  Tangent vector delta = (omega, v), rotation first (radians, then the
+ * units of obj), of the left-multiplied perturbation R' = exp(omega) R, t' = exp(omega) t + v; residual = projected - observed, pixels.
+ *   rows used   i < count, inlier_mask[i] != 0, depth under the pose > 1e-6 (fp64); n of them
+ *   H = sum J_i^T J_i, cost = sum |r_i|^2 in fp64, J_i the 2 x 6 Jacobian of the refit
+ *   sigma_hat^2 = cost / (2 n - 6);  sigma^2 = sigma_px^2 if sigma_px > 0, else sigma_hat^2
+ *   info = H / sigma^2, cov = sigma^2 H^-1 through the Cholesky factorisation of D^-1/2 H D^-1/2, D = diag(H); min_pivot = the
+ *   smallest squared diagonal entry of the factor, in (0, 1]
+ * Outputs in DEVICE memory, float64: cov (36), info (36) row-major and exactly symmetric, stat (4) = {ok, n, sigma_hat^2 (0 where
+ * 2 n - 6 <= 0), min_pivot}.  ok = 0 with all-zero matrices and min_pivot 0 - never NaN or Inf - when result[0] == 0, 2 n - 6 <= 0
+ * (sigma estimated), sigma^2 is not > 0, a diagonal entry of H is not > 0, a pivot is <= 1e-12, or any accumulated or resulting value
+ * is not finite.  One launch of one wave; results are bit-reproducible.  COFI_EINVAL: a NULL operand, n_max <= 0, fx or fy not
+ * positive, sigma_px NaN.  It is NOT a model of outliers inside the gate or of the choice of the consensus set. */
+int cofi_pose_covariance(const float *obj, const float *img, const int32_t *count_dev, int n_max, float fx, float fy, float cx, float cy,
+                         const float *pose, const int32_t *result, const uint8_t *inlier_mask, float sigma_px, double *cov, double *info,
+                         double *stat, cofi_stream_t stream);
+/* The same for the `frames` frames of cofi_pnp_ransac_batch in one launch (one wave per frame): the operands up to `frames` are read
+ * exactly as that call reads them, pose (frames, 12), result (frames, 3), inlier_mask (frames, n_max) are its outputs.  cov, info
+ * (frames, 36), stat (frames, 4).  A frame whose fx or fy is not positive has ok = 0.  Frame f is bit-identical to
+ * cofi_pose_covariance on that frame's operands. */
+int cofi_pose_covariance_batch(const float *obj, int obj_frame_stride, const float *img, int img_frame_stride, int coord_major,
+                               const int32_t *count_dev, int count_stride, const float *K_dev, int n_max, int frames, const float *pose,
+                               const int32_t *result, const uint8_t *inlier_mask, float sigma_px, double *cov, double *info, double *stat,
+                               cofi_stream_t stream);
+/* One covariance per RIG, in the rig's tangent space (perturbations of rig <- cloud): the operands of cofi_pnp_ransac_rig up to `rigs`,
+ * its rig_pose (rigs, 12) and rig_result (rigs, 3), and its per-image inlier_mask (rigs C, n_max).  Rows of every camera with usable
+ * intrinsics enter, camera-major, with the rig refit's Jacobian d(pi)/dY_c . R_c . [-[Y_rig]x | I]; a rig none of whose cameras is
+ * usable has ok = 0.  cov, info (rigs, 36), stat (rigs, 4).  The covariance of camera c's pose E_c o T follows by the adjoint of E_c. */
+int cofi_pose_covariance_rig(const float *obj, int obj_frame_stride, const float *img, int img_frame_stride, int coord_major,
+                             const int32_t *count_dev, int count_stride, const float *K_dev, const float *ext_dev, int ext_rig_stride,
+                             int n_max, int cameras, int rigs, const float *rig_pose, const int32_t *rig_result, const uint8_t *inlier_mask,
+                             float sigma_px, double *cov, double *info, double *stat, cofi_stream_t stream);
+/* Normalised estimation error squared of `frames` poses against ground truth: omega = log(R_gt R_est^T), v = t_gt - exp(omega) t_est,
+ * e = (omega, v), nees = e^T info e; NaN where stat[4 f] == 0.  pose (frames, 12); P_gt (frames, 4, 4) row-major in the direction of
+ * the pose, float64 if gt_is_f64 != 0, else float32; info (frames, 36), stat (frames, 4) as cofi_pose_covariance* write them; nees
+ * (frames) float64.  One thread per pose. */
+int cofi_pose_nees(const float *pose, const void *P_gt, int gt_is_f64, const double *info, const double *stat, int frames, double *nees,
+                   cofi_stream_t stream);
 /* The evaluation pass (evaluation/eval_all.py:107-117 and evaluation/IR_RMSE.py:36-59) for the `frames` frames of a stack-mode
  * submission, behind cofi_pnp_ransac_batch: one launch, one 256-thread workgroup per frame, no host read.  obj, img, count_dev, K_dev,
  * n_max and their strides are those of cofi_pnp_ransac_batch (a negative count is read as 0); pose (frames, 12) and result (frames, 3)
