@@ -104,6 +104,8 @@ SIGNATURES = {
     "cofi_attention_fwd": (_I, [_P, _I, _P, _I, _P, _I, _P, _P, _I, _I, _I, _I, _I, _F, _P, _Z, _I, _P]),
     "cofi_attention_fwd_colpart": (_I, [_P, _I, _P, _I, _P, _I, _P, _I, _I, _F, _P, _I, _I, _I, _I, _I, _F, _P, _Z, _I, _P]),
     "cofi_col_inv_norm": (_I, [_P, _I, _I, _I, _F, _P, _P]),
+    "cofi_linear_attention_workspace": (_Z, [_I, _I, _I, _I, _I]),
+    "cofi_linear_attention": (_I, [_P, _I, _P, _I, _P, _I, _P, _I, _I, _I, _I, _F, _I, _P, _I, _P, _Z, _P]),
     "cofi_pos_sine": (_I, [_P, _I, _I, _I, _P, _I, _I, _I, _P, _I, _P]),
     "cofi_l2norm_rows": (_I, [_P, _I, _I, _I, _P, _I, _I, _P]),
     "cofi_l2norm_rows2": (_I, [_P, _I, _I, _I, _P, _I, _P, _I, _P]),

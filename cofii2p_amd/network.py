@@ -85,11 +85,13 @@ class CoFiI2P(nn.Module):
     DEFAULT_GRAPHS = False
     MAX_COPY_GRAPHS = 8         # input signatures (sizes) whose staged-input graphs are kept; the oldest is dropped beyond that
 
-    def __init__(self, opt, init: str = "synthetic", arithmetic: Optional[str] = None):
+    def __init__(self, opt, init: str = "synthetic", arithmetic: Optional[str] = None, attention: Optional[str] = None):
         super().__init__()
         self.opt = opt
         self.arithmetic = arithmetic if arithmetic is not None else getattr(opt, "arithmetic", self.DEFAULT_ARITHMETIC)
         ops.arithmetic(self.arithmetic)   # validates the name
+        # ATTENTION of transformer.py:12: fixed for the life of the instance (so its graph cache holds one kind only); no parameters depend on it
+        self.attention = transformer.check_attention(attention if attention is not None else getattr(opt, "attention", "full"))
         self.pc_norm_kind = getattr(opt, "norm", "gn")   # get_norm() of the point encoder: 'gn' (shipped), 'bn' (running statistics), 'ln'
         if self.pc_norm_kind not in ("gn", "bn", "ln"):
             raise ValueError("only support batch normalization, layer normalization and group normalization now!")   # modules.py:60
@@ -296,7 +298,7 @@ class CoFiI2P(nn.Module):
         img_desc_t = torch.empty((C, T_img), dtype=torch.float32, device=dev) if B == 1 else None
         pc_desc_t = torch.empty((C, N4), dtype=torch.float32, device=dev) if B == 1 else None
         tok_img, tok_pc, l2_done = transformer.run_transformer(self._layers, LAYER_KINDS, ts, N_HEAD, frames=B,
-                                                               l2=(img_desc_tok, pc_desc_tok, img_desc_t, pc_desc_t))
+                                                               l2=(img_desc_tok, pc_desc_tok, img_desc_t, pc_desc_t), attention=self.attention)
 
         # ---- scores + coarse descriptors (network.py:123-126)
         pc_score = self._score_head(P, "pc_score_layer", tok_pc, B)  # (B*N4,1)

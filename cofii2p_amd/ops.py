@@ -1195,6 +1195,48 @@ def attention(q, k, v, q_colscale=None, nhead: int = 4, out=None, frames: int = 
     return res if parts else res.merge(out)
 
 
+_WS_LINATTN = Workspace()
+
+
+def linear_attention(q, k, v, q_colscale=None, q_colpart=None, nhead: int = 4, frames: int = 1, out=None, eps: float = 1e-6, q_eps: float = 1e-12):
+    """LoFTR linear attention (cofi_linear_attention; linear_attention.py:14-47) -> the plain (frames*L, H*D) matrix.  Operands as for
+    `attention`: q (frames*L, HD), k / v (frames*S, HD) - column slices of a projection buffer are fine -, q_colscale (frames, HD), or
+    q_colpart (nslab, ncols, 2): the column partials of the GEMM / fused tail that produced q (its first HD columns), turned into the
+    per-frame token-axis scale by cofi_col_inv_norm_from_colpart (slabs must not straddle frames).  fp32 FMA whatever COFI_GEMM / COFI_ATTN say."""
+    lib = _lib.load()
+    _mat(q, "q"), _mat(k, "k", device=q.device), _mat(v, "v", device=q.device)
+    L, HD = q.shape
+    S = k.shape[0]
+    if k.shape[1] != HD or tuple(v.shape) != (S, HD) or HD % nhead:
+        raise _lib.CofiError("linear_attention: q %s, k %s, v %s do not hold %d heads of one width" % (tuple(q.shape), tuple(k.shape), tuple(v.shape), nhead))
+    D = HD // nhead
+    if L % frames or S % frames:
+        raise _lib.CofiError("linear_attention: rows are not a multiple of the frame count")
+    L, S = L // frames, S // frames
+    nbytes = lib.cofi_linear_attention_workspace(L, S, nhead, D, frames)
+    if nbytes == 0:
+        raise _lib.CofiError("linear_attention: unsupported shape (head dimension must be 32)")
+    if q_colscale is not None and q_colpart is not None:
+        raise _lib.CofiError("linear_attention: q_colscale and q_colpart are alternatives")
+    if q_colpart is not None:
+        nslab = q_colpart.shape[0]
+        if (q_colpart.dim() != 3 or q_colpart.shape[2] != 2 or q_colpart.shape[1] < HD or q_colpart.dtype != torch.float32 or not q_colpart.is_contiguous()
+                or q_colpart.device != q.device or nslab % frames or (frames > 1 and L % 64)):
+            raise _lib.CofiError("linear_attention: q_colpart must be contiguous float32 (nslab, >= %d, 2) partials of 64-row slabs, whole per frame" % HD)
+        q_colscale = col_inv_norm_from_colpart(q_colpart, frames * L, HD, eps=q_eps, frames=frames)
+    _vec(q_colscale, "linear_attention: q_colscale", frames * HD, device=q.device)
+    if out is None:
+        out = torch.empty((frames * L, HD), dtype=torch.float32, device=q.device)
+    _mat(out, "out", device=q.device)
+    if tuple(out.shape) != (frames * L, HD):
+        raise _lib.CofiError("linear_attention: out is %s, expected %s" % (tuple(out.shape), (frames * L, HD)))
+    ws = _WS_LINATTN.get(nbytes, q.device)
+    rc = lib.cofi_linear_attention(_p(q), _ld(q), _p(k), _ld(k), _p(v), _ld(v), _p(q_colscale), L, S, nhead, D, eps, frames, _p(out), _ld(out),
+                                   _p(ws), ws.numel(), _stream())
+    _lib.check(rc, "cofi_linear_attention")
+    return out
+
+
 def split_bf16(w: torch.Tensor):
     """fp32 -> (hi, lo) bf16 planes as int16 tensors: hi = bf16(w) (RNE), lo = bf16(w - hi)."""
     hi = w.to(torch.bfloat16)

@@ -197,7 +197,36 @@ def image_upsample(P, B, name, low, h, w, skip, training):
 
 
 # ------------------------------------------------------------------------------------------ transformer (transformer.py:43-104)
-def loftr_layer(P, p, x, src, nhead: int = N_HEAD):
+_HEAD_MASKS = {}
+
+
+def _head_mask(C: int, nhead: int, device) -> torch.Tensor:
+    """(C, C) constant: 1 where row and column belong to the same head."""
+    key = (C, nhead, str(device))
+    if key in _HEAD_MASKS:
+        return _HEAD_MASKS[key]
+    head = torch.arange(C, device=device) // (C // nhead)
+    mask = (head[:, None] == head[None, :]).to(torch.float32)
+    if not torch.cuda.is_current_stream_capturing():   # (a tensor first made while a hipGraph records lives in that graph: not kept)
+        _HEAD_MASKS[key] = mask
+    return mask
+
+
+def linear_attention(q, k, v, nhead: int = N_HEAD, eps: float = 1e-6):
+    """linear_attention.py:31-47 on (L, C) / (S, C) matrices (q already scaled), composed from differentiable operators: the two
+    contractions over the tokens are ag.linear (HIP forward and backward) on all heads at once, the off-head blocks of the (C, C) summary
+    removed by a constant block-diagonal mask; the feature map and the normaliser are elementwise torch."""
+    L, C = q.shape
+    S = k.shape[0]
+    fq, fk = F.elu(q) + 1, F.elu(k) + 1
+    kv = ag.linear(fk.t(), (v / S).t()) * _head_mask(C, nhead, q.device)          # (C, C): [d, v] = sum_s phi(k)[s, d] v[s, v] / S
+    num = ag.linear(fq, kv.t())                                                   # (L, C)
+    den = (fq * fk.sum(0)).view(L, nhead, C // nhead).sum(2)                      # (L, H)
+    z = 1 / (den + eps)
+    return (num.view(L, nhead, C // nhead) * z[:, :, None] * S).reshape(L, C)
+
+
+def loftr_layer(P, p, x, src, nhead: int = N_HEAD, attention: str = "full"):
     C = x.shape[1]
     if src is x:   # self layer: the three projections read the same tokens - one contraction with the stacked weights [Wq; Wk; Wv]
         qkv = ag.linear(x, torch.cat([P[p + "q_proj.weight"], P[p + "k_proj.weight"], P[p + "v_proj.weight"]], 0))
@@ -207,21 +236,21 @@ def loftr_layer(P, p, x, src, nhead: int = N_HEAD):
         kv = ag.linear(src, torch.cat([P[p + "k_proj.weight"], P[p + "v_proj.weight"]], 0))
         k, v = kv.split(C, 1)
     q = ag.normalize_cols(q)    # transformer.py:53: F.normalize's default dim=1 on (1, L, H, D) = over the L tokens
-    msg = ag.attention(q, k, v, nhead)
+    msg = linear_attention(q, k, v, nhead) if attention == "linear" else ag.attention(q, k, v, nhead)
     msg = F.layer_norm(ag.linear(msg, P[p + "merge.weight"]), (C,), P[p + "norm1.weight"], P[p + "norm1.bias"])
     h = ag.linear(F.relu(ag.linear(torch.cat([x, msg], 1), P[p + "mlp.0.weight"])), P[p + "mlp.2.weight"])
     return x + F.layer_norm(h, (C,), P[p + "norm2.weight"], P[p + "norm2.bias"])
 
 
-def transformer(P, tok_img, tok_pc):
+def transformer(P, tok_img, tok_pc, attention: str = "full"):
     for l, kind in enumerate(LAYER_KINDS):
         p = "transformer.layers.%d." % l
         if kind == "self":
-            tok_img = loftr_layer(P, p, tok_img, tok_img)
-            tok_pc = loftr_layer(P, p, tok_pc, tok_pc)
+            tok_img = loftr_layer(P, p, tok_img, tok_img, attention=attention)
+            tok_pc = loftr_layer(P, p, tok_pc, tok_pc, attention=attention)
         else:   # the point stream attends to the ALREADY UPDATED image stream (transformer.py:99-100)
-            tok_img = loftr_layer(P, p, tok_img, tok_pc)
-            tok_pc = loftr_layer(P, p, tok_pc, tok_img)
+            tok_img = loftr_layer(P, p, tok_img, tok_pc, attention=attention)
+            tok_pc = loftr_layer(P, p, tok_pc, tok_img, attention=attention)
     return tok_img, tok_pc
 
 
@@ -308,7 +337,7 @@ def forward_train(model, pc_data_dict: Dict, img: torch.Tensor, fine_center_kpt_
     if fork:
         main.wait_event(tokens_ready)
         tok_img.record_stream(main)
-    tok_img, tok_pc = transformer(P, tok_img, tok_pc)
+    tok_img, tok_pc = transformer(P, tok_img, tok_pc, getattr(model, "attention", "full"))
     pc_score = score_head(P, "pc_score_layer", tok_pc)
     img_score = score_head(P, "img_score_layer", tok_img)
     pc_desc = ag.normalize_rows(tok_pc).t()                                  # (C, N4)  network.py:125

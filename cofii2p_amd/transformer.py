@@ -45,9 +45,20 @@ def pack_layer(sd: Dict[str, torch.Tensor], p: str) -> Dict[str, torch.Tensor]:
     return out
 
 
-def _layer(w, xcat: torch.Tensor, src: torch.Tensor, out: torch.Tensor, self_attn: bool, nhead: int = 4, frames: int = 1):
+ATTENTION_KINDS = ("full", "linear")   # transformer.py:12 (ATTENTION)
+
+
+def check_attention(kind: str) -> str:
+    if kind not in ATTENTION_KINDS:
+        raise ValueError("attention must be one of %s, got %r" % (ATTENTION_KINDS, kind))
+    return kind
+
+
+def _layer(w, xcat: torch.Tensor, src: torch.Tensor, out: torch.Tensor, self_attn: bool, nhead: int = 4, frames: int = 1,
+           attention: str = "full"):
     """xcat (L,2C): x in [:, :C]; src (S,C) view; out (L,C) view receiving x + message.
-    transformer.py:43-64."""
+    transformer.py:43-64.  attention: 'full' (softmax, FullAttention) or 'linear' (LinearAttention, ops.linear_attention: its output is
+    the plain message matrix, which the fused tail and the merge GEMM both take)."""
     C = xcat.shape[1] // 2
     x = xcat[:, :C]
     # projections; the token-axis norm of Q (F.normalize over dim=1, transformer.py:53) comes from the GEMM's
@@ -62,7 +73,13 @@ def _layer(w, xcat: torch.Tensor, src: torch.Tensor, out: torch.Tensor, self_att
     # the attention kernel folds the partials into the per-frame token-axis norm of Q itself
     fused_tail = ops.tail_planes() > 0 and C == 128 and x.shape[0] <= TAIL_MAX_ROWS
     rows_q = x.shape[0] // frames
-    if frames > 1 and rows_q % 64:   # the projection's 64-row statistics slabs straddle frames: explicit per-frame column norms
+    if attention == "linear":
+        if frames > 1 and rows_q % 64:
+            qs = torch.stack([ops.col_inv_norm(q[f * rows_q:(f + 1) * rows_q]) for f in range(frames)])
+            msg = ops.linear_attention(q, k, v, q_colscale=qs, nhead=nhead, frames=frames)
+        else:
+            msg = ops.linear_attention(q, k, v, q_colpart=part, nhead=nhead, frames=frames)
+    elif frames > 1 and rows_q % 64:   # the projection's 64-row statistics slabs straddle frames: explicit per-frame column norms
         qs = torch.stack([ops.col_inv_norm(q[f * rows_q:(f + 1) * rows_q]) for f in range(frames)])
         msg = ops.attention(q, k, v, q_colscale=qs, nhead=nhead, frames=frames, parts=fused_tail)
     else:
@@ -79,16 +96,17 @@ def _layer(w, xcat: torch.Tensor, src: torch.Tensor, out: torch.Tensor, self_att
     return out
 
 
-def loftr_layer(w, x: torch.Tensor, src: torch.Tensor, nhead: int = 4) -> torch.Tensor:
+def loftr_layer(w, x: torch.Tensor, src: torch.Tensor, nhead: int = 4, attention: str = "full") -> torch.Tensor:
     """Stand-alone layer on plain (L,C)/(S,C) tensors (tests); `w` holds raw reference-named weights
     or a packed dict."""
+    check_attention(attention)
     if "kv.weight" not in w:
         w = pack_layer(w, "")
     L, C = x.shape
     xcat = torch.empty((L, 2 * C), dtype=torch.float32, device=x.device)
     xcat[:, :C].copy_(x)
     out = torch.empty((L, C), dtype=torch.float32, device=x.device)
-    return _layer(w, xcat, src, out, self_attn=False, nhead=nhead)
+    return _layer(w, xcat, src, out, self_attn=False, nhead=nhead, attention=attention)
 
 
 class TokenStreams:
@@ -173,12 +191,15 @@ def _run_chain(layers, kinds, ts: "TokenStreams", nhead: int, frames: int, l2=No
     return ts.img_tokens(), ts.pc_tokens()
 
 
-def run_transformer(layers, kinds, ts: TokenStreams, nhead: int = 4, frames: int = 1, l2=None):
+def run_transformer(layers, kinds, ts: TokenStreams, nhead: int = 4, frames: int = 1, l2=None, attention: str = "full"):
     """transformer.py:85-104.  Self layers share weights between the streams; in a cross layer the
     point stream attends to the ALREADY UPDATED image stream (:99-100).  l2 (optional, the fused chain only - see _run_chain):
-    destinations for the L2-normalised outputs; returns (img tokens, pc tokens, l2 written?)."""
+    destinations for the L2-normalised outputs; returns (img tokens, pc tokens, l2 written?).  attention='linear' runs layer by layer
+    (joint self layers, fused tails and stack mode included): the chain's tails hand on 32-row column partials and the softmax kernel's
+    slot table, neither of which the linear operator reads."""
     C = ts.C
-    if _chain_ok(ts, kinds, frames):
+    check_attention(attention)
+    if attention == "full" and _chain_ok(ts, kinds, frames):
         ti, tp = _run_chain(layers, kinds, ts, nhead, frames, l2 if kinds[-1] == "cross" else None)
         return ti, tp, (l2 is not None and kinds[-1] == "cross")
     for w, kind in zip(layers, kinds):
@@ -187,15 +208,15 @@ def run_transformer(layers, kinds, ts: TokenStreams, nhead: int = 4, frames: int
         if kind == "self" and ts.joint and ts.cur_img == ts.cur_pc and JOINT_SELF:
             # shared weights, independent streams: one pass over [image tokens | point tokens] as 2*frames frames
             xb, ob = ts.both[ts.cur_img], ts.both[ts.cur_img ^ 1]
-            _layer(w, xb, xb[:, :C], ob[:, :C], True, nhead, 2 * frames)
+            _layer(w, xb, xb[:, :C], ob[:, :C], True, nhead, 2 * frames, attention)
         elif kind == "self":  # the two modalities are independent here: point stream on a side HIP stream
             with ops.Branch(xi.device, 2) as br:
-                _layer(w, xp, xp[:, :C], op[:, :C], True, nhead, frames)
-            _layer(w, xi, xi[:, :C], oi[:, :C], True, nhead, frames)
+                _layer(w, xp, xp[:, :C], op[:, :C], True, nhead, frames, attention)
+            _layer(w, xi, xi[:, :C], oi[:, :C], True, nhead, frames, attention)
             br.join(op)
         else:
-            _layer(w, xi, xp[:, :C], oi[:, :C], False, nhead, frames)
-            _layer(w, xp, oi[:, :C], op[:, :C], False, nhead, frames)
+            _layer(w, xi, xp[:, :C], oi[:, :C], False, nhead, frames, attention)
+            _layer(w, xp, oi[:, :C], op[:, :C], False, nhead, frames, attention)
         ts.cur_img ^= 1
         ts.cur_pc ^= 1
     return ts.img_tokens(), ts.pc_tokens(), False

@@ -425,6 +425,23 @@ int cofi_attention_fwd_colpart(const float *Q, int ldq, const float *K, int ldk,
 int cofi_col_inv_norm(const float *x, int ldx, int M, int C, float eps, float *out, cofi_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * K6b  LoFTR linear attention, model/transformer/linear_attention.py:14-47 (`LinearAttention.forward`, no masks) with the token-axis
+ * query scaling of transformer.py:53 (q' = q * q_colscale).  Per frame and head, phi(x) = elu(x) + 1:
+ *   KV[d,v] = sum_s phi(k)[s,d] * (v[s,v] / S)     Ksum[d] = sum_s phi(k)[s,d]
+ *   O[l, h*D + v] = (sum_d phi(q')[l,d] * KV[d,v]) * (1 / (sum_d phi(q')[l,d] * Ksum[d] + eps)) * S
+ * Operands as for cofi_attention_parts: Q (frames*L, H*D) ldq; K, V (frames*S, H*D) ldk / ldv (column slices of a wider projection
+ * buffer are fine: 16-byte aligned, leading dimensions multiples of 4); q_colscale (frames, H*D) or NULL; O (frames*L, H*D) ldo.  D == 32.
+ * fp32 FMA throughout.  A summary launch over (128-row source chunk, head, frame) leaves one partial KV / Ksum per chunk in `ws`, a fold
+ * launch sums them in a fixed order, an apply launch serves 64 query rows per workgroup: no floating-point atomics, the chunking depends on
+ * S alone, so frame f of a stacked call has the bits of the single-frame call on its slice.  phi flushes exp() results below the smallest
+ * normal number to zero: keys that are all very negative give O = 0 exactly.
+ *   cofi_linear_attention_workspace  bytes of `ws` (16-byte aligned device memory); 0 = unsupported shape (D != 32)
+ */
+size_t cofi_linear_attention_workspace(int L, int S, int H, int D, int frames);
+int cofi_linear_attention(const float *Q, int ldq, const float *K, int ldk, const float *V, int ldv, const float *q_colscale, int L, int S,
+                          int H, int D, float eps, int frames, float *O, int ldo, void *ws, size_t ws_bytes, cofi_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * K7  fused tail of one LoFTR encoder layer (d_model = 128), one kernel:
  *   out = x + LN2( relu([x | LN1(msg Wm^T)] W0^T) W2^T )         model/transformer/transformer.py:57-64
  * msg (L,128) ldm = attention output; x (L,128) ldx = layer input; weights PRE-SPLIT into bf16 hi/lo planes
