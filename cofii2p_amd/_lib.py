@@ -196,7 +196,15 @@ TUNE_SIGNATURES = {
     "cofi_tune_big_debug": (_I, [_I]),
     "cofi_tune_f16x3_resplit_events": (ctypes.c_long, [_I]),
     "cofi_tune_f16x3_launch_flops": (ctypes.c_long, [_I, _P]),
+    "cofi_tune_describe_gemm": (_I, [_I, _I, _I, _I, _I, _I, _I, _Z, _P]),
+    "cofi_tune_describe_conv": (_I, [_I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _Z, _P]),
 }
+
+
+class PlanDesc(ctypes.Structure):
+    """cofi_plan_desc_t (include/cofi_hip_tune.h): what cofi_tune_describe_gemm / _conv fill in."""
+    _fields_ = [("status", c_int), ("family", c_int), ("bm", c_int), ("bn", c_int), ("ksplit", c_int), ("kchunk", c_int), ("pcfg", c_int),
+                ("partial_bytes", ctypes.c_longlong), ("flag_offset", ctypes.c_longlong), ("ws_bytes", ctypes.c_longlong)]
 
 
 def header_symbols(path=None):

@@ -19,7 +19,10 @@ static inline int cofi_launch_status() {
 
 static inline hipStream_t cofi_s(cofi_stream_t s) { return (hipStream_t)s; }
 
+#ifndef COFI_CDIV_DEFINED   // (gemm_planner.h, plain host C++, carries the same line)
+#define COFI_CDIV_DEFINED
 static inline int cofi_cdiv(long a, long b) { return (int)((a + b - 1) / b); }
+#endif
 
 __device__ __forceinline__ int lane_id() { return threadIdx.x & 63; }
 

@@ -1146,252 +1146,18 @@ __global__ __launch_bounds__(256) void splitk_epilogue_ln_kernel(GemmArgs g) {
     rowwise_epilogue<SKLN_ROWS, 128, true>(g, nullptr, 0, blockIdx.y * SKLN_ROWS, blockIdx.x * 128, blockIdx.y, nullptr);
 }
 
-struct Plan {
-    int bm, bn, ksplit, kchunk;
-    int pcfg;   // >= 0: gemm_planes_kernel configuration (kPlanesCfg) - both operands are bf16 planes; -1: the register-staged kernels
-    int big;    // 1: gemm_x6_big_kernel (bf16x6, 256 x 128 tile, one workgroup per CU)
-};
+}  // namespace
 
-// Configurations of gemm_planes_kernel: tile, K-tile depth, wave grid, LDS stages, workgroups per CU the register budget allows.
-struct PlanesCfg { int bm, bn, bk, wm, wn, nst, minw; };
-#define COFI_PLANES_CFGS(X)          \
-    X(0, 128, 128, 64, 4, 2, 2, 2)   \
-    X(1, 64, 64, 64, 2, 2, 2, 2)     \
-    X(2, 256, 128, 32, 4, 2, 3, 2)   \
-    X(3, 256, 256, 32, 4, 2, 2, 2)   \
-    X(4, 128, 32, 64, 4, 1, 2, 2)    \
-    X(5, 128, 64, 64, 4, 2, 2, 2)    \
-    X(6, 64, 64, 32, 2, 2, 4, 2)     \
-    X(7, 128, 128, 32, 4, 2, 4, 2)   \
-    X(8, 64, 128, 64, 2, 2, 2, 1)
-static const PlanesCfg kPlanesCfg[] = {
-#define X(id, bm, bn, bk, wm, wn, nst, minw) {bm, bn, bk, wm, wn, nst, minw},
-    COFI_PLANES_CFGS(X)
-#undef X
-};
-constexpr int kNumPlanesCfg = sizeof(kPlanesCfg) / sizeof(kPlanesCfg[0]);
+// The host side from here on.  Which kernel, tile, K split and workspace layout a contraction gets is decided in gemm_planner.h alone
+// (PlanRequest -> status + Plan); the entries below validate operands, ask it, fill GemmArgs from request and plan, and call launch().
+#include "gemm_planner.h"
 
-// Tuned plans for the shapes of the KITTI / nuScenes-shaped forward (tools/tune_gemm.py on MI355X, bf16x3 kernel):
-// {M, N, K, bm, bn, ksplit}.  Anything not listed falls through to the heuristic below.
-struct TunedPlan { int M, N, K, bm, bn, ks; };
-#include "gemm_plans.inc"
-// ... and for the bf16x6 kernel (twice the MFMAs and 1.5x the LDS traffic per K-tile move the best split): tools/tune_gemm.py --gemm bf16x6
-#include "gemm_plans_x6.inc"
+namespace {
 
-// Tuning / test hooks (include/cofi_hip_tune.h): plan overrides of the CALLING THREAD only - plans are chosen on the thread that enqueues a
-// launch, so a tool or a test that forces a plan cannot change the launches of any other thread; the product path never sets them.
-thread_local int g_force_bm = 0, g_force_bn = 0, g_force_ks = 0;
+static_assert(PLAN_BK == BK, "the planner's K-tile is the register-staged kernels'");
 
-Plan finish_plan(int K, int bm, int bn, int ks) {
-    Plan p;
-    p.pcfg = -1;
-    p.big = 0;
-    p.bm = bm; p.bn = bn;
-    int ktiles = cofi_cdiv(K, BK);
-    if (ks < 1) ks = 1;
-    int tiles_per = cofi_cdiv(ktiles, ks);
-    tiles_per = (tiles_per + 3) & ~3;  // k-chunks in multiples of 128: the bf16x3 kernel steps K by 128
-    p.kchunk = tiles_per * BK;
-    p.ksplit = cofi_cdiv(K, p.kchunk);
-    return p;
-}
-
-// Heuristic: largest tile that still gives >= ~1 workgroup per CU, then split K until the chip
-// (256 CUs) is covered about twice, keeping >= 2 k-tiles (64 values) per split.
-Plan make_plan_base(int M, int N, int K, bool fused_ln, int arith) {
-    Plan p;
-    p.pcfg = -1;
-    p.big = 0;
-    if (g_force_bm) {
-        p = finish_plan(K, g_force_bm, (g_force_bm == 128 && g_force_bn == 64 && arith != 2) ? 128 : g_force_bn, g_force_ks);   // 128 x 64: bf16x6 only
-        if (fused_ln && p.ksplit == 1 && p.bn < N) { p.bm = 64; p.bn = 128; }
-        return p;
-    }
-    static const bool x6_table = !(getenv("COFI_GEMM_X6_PLANS") && atoi(getenv("COFI_GEMM_X6_PLANS")) == 0);   // A/B switch (tools)
-    if (arith == 2 && x6_table)
-        for (const TunedPlan &t : kTunedPlansX6)
-            if (t.M == M && t.N == N && t.K == K) {
-                p = finish_plan(K, t.bm, t.bn, t.ks);
-                if (fused_ln && p.ksplit == 1 && p.bn < N) { p.bm = 64; p.bn = 128; }
-                return p;
-            }
-    for (const TunedPlan &t : kTunedPlans)
-        if (t.M == M && t.N == N && t.K == K) {
-            p = finish_plan(K, t.bm, t.bn, t.ks);
-            if (fused_ln && p.ksplit == 1 && p.bn < N) { p.bm = 64; p.bn = 128; }
-            return p;
-        }
-    auto blocks = [&](int bm, int bn) { return (long)cofi_cdiv(M, bm) * cofi_cdiv(N, bn); };
-    if (N > 64 && M > 64 && blocks(128, 128) >= 200) {
-        p.bm = 128; p.bn = 128;
-    } else if (N > 64 && blocks(64, 128) >= 200) {
-        p.bm = 64; p.bn = 128;
-    } else if (N > 32) {
-        p.bm = 64; p.bn = 64;
-        if (N > 64 && blocks(64, 128) * 2 >= blocks(64, 64) && blocks(64, 64) > 1024) { p.bn = 128; }
-    } else {
-        p.bm = 64; p.bn = 64;
-    }
-    long nb = blocks(p.bm, p.bn);
-    int ktiles = cofi_cdiv(K, BK);
-    int ks = 1;
-    // Split K only when the serial k-loop is long: a split costs a second kernel (the reduction epilogue,
-    // ~5 us of launch + latency), which a loop of <= 16 k-tiles (K <= 512) cannot win back.
-    if (nb < 384 && ktiles > 16) {
-        ks = (int)((512 + nb - 1) / nb);
-        int maxks = ktiles / 8;  // >= 256 k-values per split
-        if (maxks < 1) maxks = 1;
-        if (ks > maxks) ks = maxks;
-        if (ks > 32) ks = 32;
-    }
-    int tiles_per = cofi_cdiv(ktiles, ks);
-    tiles_per = (tiles_per + 3) & ~3;  // k-chunks in multiples of 128: the bf16x3 kernel steps K by 128
-    p.kchunk = tiles_per * BK;
-    p.ksplit = cofi_cdiv(K, p.kchunk);
-    if (fused_ln && p.ksplit == 1 && p.bn < N) {  // un-split: one tile must span the whole row (N <= 128)
-        p.bm = 64;
-        p.bn = 128;
-    }
-    return p;
-}
-
-// bf16x6, <= 64 output columns over many rows (stack-mode batches of >= 4 frames): a 128 x 64 tile (waves of 64 x 32) splits a W tile once
-// per 128 rows instead of once per 64 and reads 3/4 of the fragment bytes per MFMA.  Measured on the batch-16 shapes (tools/tall_tile_probe.py,
-// outputs bit-equal to the 64 x 64 tile's): -12 ... -31 % per launch from 640 tiles up (M >= 81920), +-3 % at 320 tiles, +35 % at 160 - hence
-// the threshold.  COFI_GEMM_TALL_TILE=0 switches it off (A/B), any other value is the threshold in tiles.
-Plan make_plan(int M, int N, int K, bool fused_ln, int arith = 1) {   // arith: GemmArgs::bf16x3 (2 = bf16x6: its own table first)
-    Plan p = make_plan_base(M, N, K, fused_ln, arith);
-    static const long tall = getenv("COFI_GEMM_TALL_TILE") ? atol(getenv("COFI_GEMM_TALL_TILE")) : 512;
-    if (arith == 2 && !g_force_bm && tall > 0 && p.pcfg < 0 && p.bm == 64 && p.bn == 64 && p.ksplit == 1 && N <= 64 &&
-        (long)cofi_cdiv(M, 128) * cofi_cdiv(N, 64) >= tall)
-        p.bm = 128;
-    return p;
-}
-
-// ---- gemm_x6_big_kernel (256 x 128 tiles, ONE workgroup per CU): which shapes take it, and with which K split.
-// One workgroup per CU means whole rounds of 256 workgroups: a grid of 320 tiles takes two rounds like one of 512.  The split is chosen
-// to minimise  rounds x (k-tiles per workgroup + fixed cost)  plus the partial-sum traffic a split adds (ks x M x N x 4 bytes written
-// and read again), in units of one K-tile of the main loop (~1.5 us).
-// tuning hook (tools only): g_force_big = 1 forces the kernel on every eligible launch (split g_force_big_ks, 0 = chosen here), -1 disables it
-thread_local int g_force_big = 0, g_force_big_ks = 0, g_big_dbg = 0;
 thread_local long g_f16_launches = 0;     // launches of the calling thread that took gemm_f16_big_kernel, and their 2 M N K (cofi_tune_f16x3_launch_flops)
 thread_local double g_f16_flops = 0.0;
-thread_local int g_force_direct = 0;   // tools / tests: 1 = the direct 3 x 3 kernel on every eligible convolution (no tile-count threshold), 2 = ... with 4-row tiles, -1 = never, 0 = default
-struct TunedBig { int M, N, K, ks; };   // ks = 0: keep the small-tile kernel for this shape
-#include "gemm_plans_big.inc"
-
-bool big_plan(int M, int N, int K, Plan &p, bool f16 = false) {   // f16: the launch will run gemm_f16_big_kernel (COFI_GEMM_F16X3)
-    static const int mode = getenv("COFI_GEMM_BIG") ? atoi(getenv("COFI_GEMM_BIG")) : 1;   // A/B switch: 0 = never
-    if (g_force_big < 0 || (mode == 0 && g_force_big == 0) || g_force_bm) return false;
-    // N <= 64: the 256 x 64 instantiation of the kernel (four waves of 64 x 64) exists in the template and is bit-equal, but LOSES to the
-    // 128 x 64 small tiles (round 5 probe, profiles/r05/big_gemm_probe_n64.txt: 327680 x 64 x 576 222 vs 209 us, 81920 x 64 x 576 80 vs 64 us -
-    // the split of the A operand is 4.6 VALU instructions per MFMA there, and one workgroup per CU has nobody to overlap them with): not built.
-    if ((K % 32) || N < 128 || M < 256) return false;
-    const int bn = 128;
-    const long tiles = (long)cofi_cdiv(M, 256) * cofi_cdiv(N, bn);
-    const int ktiles = K / 32;
-    int ks = 0;
-    if (g_force_big > 0 && g_force_big_ks > 0) ks = g_force_big_ks;
-    if (!ks && g_force_big == 0) {
-        bool listed = false;
-        static const int f16_table = getenv("COFI_GEMM_F16_TABLE") ? atoi(getenv("COFI_GEMM_F16_TABLE")) : 1;   // A/B switch: 0 = the six-product kernel's table and thresholds
-        if (!f16_table) f16 = false;
-        if (f16)
-            for (const TunedBig &t : kTunedBigF16)
-                if (t.M == M && t.N == N && t.K == K) { ks = t.ks; listed = true; break; }
-        if (!listed)
-            for (const TunedBig &t : kTunedBig)
-                if (t.M == M && t.N == N && t.K == K) { ks = t.ks; listed = true; break; }
-        if (listed && ks == 0) return false;
-        if (!listed && (tiles < 160 || K < (f16 ? 256 : 512))) return false;   // short loops / small grids: two or three small workgroups per CU overlap their prologues and epilogues
-        if (!listed && K < 512) ks = 1;
-    }
-    // The f16x3 kernel never splits K from this many 128 x 128 tiles up (COFI_GEMM_F16_KS1_TILES, 0 = off: the table's / cost model's splits
-    // everywhere).  A split pays for a launch that runs ALONE on the chip - it fills idle CUs - and that is how the table was measured; beside
-    // the other submissions of a pipeline its partial sums are only extra traffic and a fold launch.  Same box, frames/s with the splits /
-    // capped at 80 / never split: batch 16 827 / 837 / 842 (another box 825 at 80, 824 never), batch 1 511 / 515 / 506, stress (one frame,
-    // nothing else in flight) 59.5 / - / 58.4 with 59.4 at 160: small grids still need their splits (profiles/r06/ab_ks1*.txt).
-    static const long ks1_tiles = getenv("COFI_GEMM_F16_KS1_TILES") ? atol(getenv("COFI_GEMM_F16_KS1_TILES")) : 80;
-    if (f16 && ks1_tiles > 0 && g_force_big == 0 && (long)cofi_cdiv(M, 128) * cofi_cdiv(N, 128) >= ks1_tiles) ks = 1;
-    if (!ks) {
-        double best = 1e30;
-        for (int c = 1; c <= 8; ++c) {
-            const int chunk = cofi_cdiv(cofi_cdiv(ktiles, c), 4) * 4;   // k-chunks in multiples of 128, as the other kernels
-            const int eff = cofi_cdiv(ktiles, chunk);
-            if (eff != c || chunk < 8) continue;
-            // f16x3 (pre-split W): 128 x 128 tiles, two workgroups per CU; else one 256 x 128 workgroup per CU
-            const double rounds = f16 ? (double)cofi_cdiv((long)cofi_cdiv(M, 128) * cofi_cdiv(N, bn) * c, 512) : (double)cofi_cdiv(tiles * c, 256);
-            const double partial = c > 1 ? 2.0 * c * (double)M * N * 4.0 / 4.0e12 / 1.5e-6 : 0.0;   // in K-tile units
-            const double cost = rounds * (chunk + 6.0) + partial + (c > 1 ? 4.0 : 0.0);
-            if (cost < best) { best = cost; ks = c; }
-        }
-        if (!ks) return false;
-    }
-    p.pcfg = -1;
-    p.big = 1;
-    p.bm = 256; p.bn = bn;
-    const int chunk = cofi_cdiv(cofi_cdiv(ktiles, ks), 4) * 4;
-    p.kchunk = chunk * 32;
-    p.ksplit = cofi_cdiv(K, p.kchunk);
-    return true;
-}
-
-// f16x3 kernel with pre-split W: 128 x 128 tiles, two workgroups per CU, instead of one 256 x 128 workgroup (gemm_f16_big.inc).
-// Measured on the large contractions of a batch-16 forward (tools/f16_probe.py, profiles/r06/f16_probe_bm256.txt / _bm128.txt, same K splits):
-// 8.81 -> 8.28 ms per submission, 27 of 29 shapes faster.  COFI_GEMM_F16_BM256=1 / cofi_tune_big_debug bit 512 (A/B): the 256-row form.
-bool f16_two_per_cu(int M, int N, int K, const Plan &p) {
-    (void)M; (void)N; (void)K; (void)p;
-    static const int bm256 = getenv("COFI_GEMM_F16_BM256") ? atoi(getenv("COFI_GEMM_F16_BM256")) : 0;
-    return !bm256 && (g_big_dbg & 512) == 0;
-}
-
-// bytes of the f16x3 kernels' tile-flag table: one word per workgroup of a 256 x 128 launch with `ks` K-slices
-size_t f16_flag_bytes(int M, int N, int ks, int bm = 128) { return (size_t)cofi_cdiv(M, bm) * cofi_cdiv(N, 128) * ks * sizeof(unsigned); }   // (sized for the 128-row tiles: covers both forms)
-
-// ---- plans of gemm_planes_kernel (both operands pre-split): {M, N, K, configuration, split-K}, tuned on MI355X by
-// tools/tune_gemm.py --planes; anything not listed falls through to the heuristic.
-struct TunedPlanes { int M, N, K, cfg, ks; };
-#include "gemm_planes_plans.inc"
-
-// tuning hook (tools/tune_gemm.py only): cfg >= 0 forces that configuration and split, -2 sends pre-split operands to the
-// register-staged kernel instead (the A/B partner of the bit-identity test), -1 restores table + heuristic
-thread_local int g_force_pcfg = -1, g_force_pks = 0;
-
-Plan finish_planes_plan(int K, int cfg, int ks) {
-    Plan p;
-    p.pcfg = cfg;
-    p.big = 0;
-    p.bm = kPlanesCfg[cfg].bm;
-    p.bn = kPlanesCfg[cfg].bn;
-    const int ktiles = cofi_cdiv(K, 128);   // K chunks in multiples of 128, as finish_plan: equal splits give equal bits in both kernels
-    if (ks < 1) ks = 1;
-    p.kchunk = cofi_cdiv(ktiles, ks) * 128;
-    p.ksplit = cofi_cdiv(K, p.kchunk);
-    return p;
-}
-
-Plan make_planes_plan(int M, int N, int K) {
-    if (g_force_pcfg >= 0 && g_force_pcfg < kNumPlanesCfg) return finish_planes_plan(K, g_force_pcfg, g_force_pks);
-    for (const TunedPlanes &t : kTunedPlanes)
-        if (t.M == M && t.N == N && t.K == K && t.cfg >= 0 && t.cfg < kNumPlanesCfg) return finish_planes_plan(K, t.cfg, t.ks);
-    auto nblk = [&](int c) { return (long)cofi_cdiv(M, kPlanesCfg[c].bm) * cofi_cdiv(N, kPlanesCfg[c].bn); };
-    const int max_ks = K >= 1024 ? K / 512 : 1;   // >= 512 K values (4 x 128) per split
-    int cfg;
-    if (N <= 32) cfg = 4;                          // 128 x 32
-    else if (N <= 64) cfg = nblk(5) >= 400 ? 5 : 1;
-    else if (nblk(3) * max_ks >= 400 && N % 256 == 0 && M >= 8192) cfg = 3;   // 256 x 256: the L2 -> LDS traffic of a tile halves again
-    else if (nblk(2) >= 512) cfg = 2;              // 256 x 128
-    else if (nblk(0) * max_ks >= 200) cfg = 0;     // 128 x 128
-    else cfg = 1;                                  // 64 x 64
-    const long nb = nblk(cfg);
-    int ks = 1;
-    if (nb < 200) {
-        ks = (int)((256 + nb - 1) / nb);
-        if (ks > max_ks) ks = max_ks;
-        if (ks > 32) ks = 32;
-    }
-    return finish_planes_plan(K, cfg, ks);
-}
 
 // Tile order (GemmArgs::xcd): estimate the bytes both orders pull over the fabric — every XCD that touches a row panel of A
 // or a column panel of W reads it through its own L2 — and take the cheaper one.
@@ -1411,7 +1177,10 @@ int xcd_order(const GemmArgs &g, const dim3 &grid) {
     return ct < rr ? enc : 0;
 }
 
+int launch_direct(const GemmArgs &g, const Plan &p, hipStream_t s);
+
 int launch(const GemmArgs &g0, const Plan &p, hipStream_t s) {
+    if (plan_is_direct(p)) return launch_direct(g0, p, s);
     GemmArgs g = g0;
     g.ksplit = p.ksplit;
     g.kchunk = p.kchunk;
@@ -1419,7 +1188,7 @@ int launch(const GemmArgs &g0, const Plan &p, hipStream_t s) {
     g.xcd = xcd_order(g, grid);
     g.dbg = g_big_dbg;
     g.xcd_rcp_gy = grid.y > 1 ? (unsigned)((0x100000000ULL + grid.y - 1) / grid.y) : 0u;   // 0: gy = 1
-    if (p.pcfg >= 0) {
+    if (p.family == COFI_PLAN_PLANES) {
         switch (p.pcfg) {
 #define X(id, bm_, bn_, bk_, wm_, wn_, nst_, minw_)                                                                                      \
     case id:                                                                                                                             \
@@ -1438,7 +1207,7 @@ int launch(const GemmArgs &g0, const Plan &p, hipStream_t s) {
         else if (cv) hipLaunchKernelGGL((gemm_x6_big_kernel<false, true, BN_>), grid, dim3(256), 0, s, g);                   \
         else hipLaunchKernelGGL((gemm_x6_big_kernel<false, false, BN_>), grid, dim3(256), 0, s, g);                          \
     } while (0)
-        if (g.f16) {
+        if (plan_is_f16x3(p)) {
             ++g_f16_launches;
             g_f16_flops += 2.0 * g.M * g.N * g.K;
             // the pipelined kernel, then the repair launch over the same grid (its workgroups exit at once unless the first one flagged their tile)
@@ -1450,13 +1219,13 @@ int launch(const GemmArgs &g0, const Plan &p, hipStream_t s) {
         else hipLaunchKernelGGL((gemm_f16_big_kernel<false, false, ROBUST_, NW_, WPRE_, BM_>), grid, dim3(64 * NW_), 0, s, g);                     \
     } while (0)
 #define COFI_LAUNCH_F16(ROBUST_, NW_, WPRE_) COFI_LAUNCH_F16B(ROBUST_, NW_, WPRE_, 256)
-            if (g.wscale && p.bm == 128) {   // pre-split W, 128 x 128 tiles: two workgroups per CU
+            if (p.family == COFI_PLAN_BIG_F16_128) {   // pre-split W, 128 x 128 tiles: two workgroups per CU
                 COFI_LAUNCH_F16B(false, 4, true, 128);
                 COFI_LAUNCH_F16B(true, 4, true, 128);
             } else if (g.wscale) {      // pre-split W (eight-wave geometry only)
                 COFI_LAUNCH_F16(false, 8, true);
                 COFI_LAUNCH_F16(true, 8, true);
-            } else if (g.dbg & 256) {   // cofi_tune_big_debug bit 256 (A/B): the four-wave geometry
+            } else if (p.family == COFI_PLAN_BIG_F16_W4) {   // cofi_tune_big_debug bit 256 (A/B): the four-wave geometry
                 COFI_LAUNCH_F16(false, 4, false);
                 COFI_LAUNCH_F16(true, 4, false);
             } else {
@@ -1529,6 +1298,21 @@ int launch(const GemmArgs &g0, const Plan &p, hipStream_t s) {
     return cofi_launch_status();
 }
 
+// the direct 3 x 3 convolution (conv_direct.inc): one workgroup per tile of th rows x 64 pixels of a frame
+int launch_direct(const GemmArgs &g, const Plan &p, hipStream_t s) {
+    const int th = p.family == COFI_PLAN_DIRECT_4 ? 4 : 2;
+    const long tiles = (long)(g.M / g.cv_Pout) * (g.cv_H / th) * (g.cv_W / 64);
+    const dim3 grid(g.N / 64, (unsigned)tiles);
+    if (th == 4) {
+        if (g.an.part) hipLaunchKernelGGL((conv3x3_direct_kernel<true, 4>), grid, dim3(256), 0, s, g);
+        else hipLaunchKernelGGL((conv3x3_direct_kernel<false, 4>), grid, dim3(256), 0, s, g);
+    } else {
+        if (g.an.part) hipLaunchKernelGGL((conv3x3_direct_kernel<true, 2>), grid, dim3(256), 0, s, g);
+        else hipLaunchKernelGGL((conv3x3_direct_kernel<false, 2>), grid, dim3(256), 0, s, g);
+    }
+    return cofi_launch_status();
+}
+
 int check_common(const float *A, int lda, const float *W, int ldw, float *C, int ldc, int M, int N, int K) {
     if (!A || !W || !C || M < 0 || N <= 0 || K <= 0) return COFI_EINVAL;
     if ((K & 3) || (lda & 3) || (ldw & 3) || lda < K || ldw < K || ldc < N) return COFI_EINVAL;
@@ -1544,18 +1328,43 @@ int stat_shift_of(int width, int N) {
     return sh;
 }
 
-// the pending normalisation of the A operand; channels = columns of a dense A / input channels of a convolution.
-// Runs on the bf16x3 kernels with pre-split weights and on the bf16x6 kernels.
-int set_a_norm(GemmArgs &g, const cofi_norm_desc_t *a_norm, int channels, int a_rows_per_frame, int frames, const Plan &p) {
-    if (!a_norm) return 0;
-    if (!(g.bf16x3 == 1 && g.wsplit) && g.bf16x3 != 2) return COFI_EUNSUPPORTED;   // 3-term kernel: pre-split weights; 6-term kernel: fp32 or pre-split weights
+// ---- requests, as the entries, the queries and the description hooks put them to the planner
+PlanRequest gemm_request(int M, int N, int K, int act, int pending_norm, int frames, size_t ws_bytes) {
+    PlanRequest r = decode_flags(act);
+    r.M = M; r.N = N; r.K = K; r.pending_norm = pending_norm; r.frames = frames; r.ws_bytes = ws_bytes;
+    return r;
+}
+
+// cofi_gemm_f32_layernorm reads the arithmetic and COFI_GEMM_W_SPLIT from its `relu` word; it never takes the 256 x 128 kernel
+PlanRequest layernorm_request(int M, int N, int K, int relu, size_t ws_bytes) {
+    PlanRequest r = gemm_request(M, N, K, relu, 0, 1, ws_bytes);
+    r.asplit = r.l2n = r.f16 = r.wf16 = 0;
+    r.fused_ln = 1;
+    return r;
+}
+
+PlanRequest conv_request(int H, int W, int Cin, int Cout, int ks, int stride, int pad, int ldx, int act, int pending_norm, int frames, size_t ws_bytes) {
+    PlanRequest r = gemm_request(0, 0, 0, act, pending_norm, frames, ws_bytes);
+    r.H = H; r.W = W; r.Cin = Cin; r.Cout = Cout; r.ks = ks; r.stride = stride; r.pad = pad; r.ldx = ldx;
+    return r;
+}
+
+// The pending normalisation of the A operand (channels = columns of a dense A / input channels of a convolution) into g.an; the status goes
+// into the request, and the planner reports it at its place among the other refusals.
+int norm_status(GemmArgs &g, const cofi_norm_desc_t *a_norm, int channels, int a_rows_per_frame, int frames) {
     if (a_norm->channels != channels) return COFI_EINVAL;
     if (int rc = make_norm_src(a_norm, a_rows_per_frame, frames, 512, &g.an)) return rc;
     if (!(g.an.slope >= 0.f && g.an.slope <= 1.f)) return COFI_EINVAL;
-    // a tile of GEMM rows must lie inside one frame
-    g.an_rows = g.M / frames;
-    if (frames > 1 && (g.M % frames || (g.an_rows % p.bm))) return COFI_EUNSUPPORTED;
     return 0;
+}
+
+// the f16x3 kernels' operands: tile flags in the workspace where the plan put them, the panel scales of a pre-split W behind its (N, ldw) matrix
+void set_f16_args(GemmArgs &g, const PlanRequest &rq, const Plan &p, void *ws, const float *W, int ldw) {
+    if (p.flag_off >= 0) {
+        g.f16 = 1;
+        g.fixflags = reinterpret_cast<unsigned *>(static_cast<char *>(ws) + p.flag_off);
+    }
+    if (rq.wf16) g.wscale = W + (size_t)rq.N * ldw;
 }
 
 int gemm_entry(const float *A, int lda, const cofi_norm_desc_t *a_norm, const float *W, int ldw, float *C, int ldc, int M, int N, int K,
@@ -1567,162 +1376,93 @@ int gemm_entry(const float *A, int lda, const cofi_norm_desc_t *a_norm, const fl
     if (res_idx && (res_rows <= 0 || res_idx_stride <= 0 || frames <= 0 || M % frames)) return COFI_EINVAL;
     if (res_idx && (long)frames * res_rows > 0x7fffffffL) return COFI_EINVAL;   // res_src_row computes the source row as an int
     if (M == 0) return 0;
-    const int bf16x3 = (act & COFI_GEMM_BF16X6) ? 2 : ((act & COFI_GEMM_BF16X3) ? 1 : 0);
-    const int wsplit = (act & COFI_GEMM_W_SPLIT) ? 1 : 0;
-    const int asplit = (act & COFI_GEMM_A_SPLIT) ? 1 : 0;
-    const int l2n = (act & COFI_GEMM_L2NORM) ? 1 : 0;
-    const int f16 = (act & COFI_GEMM_F16X3) ? 1 : 0;
-    const int wf16 = (act & COFI_GEMM_W_F16PRE) ? 1 : 0;
-    act &= ~(COFI_GEMM_BF16X3 | COFI_GEMM_BF16X6 | COFI_GEMM_W_SPLIT | COFI_GEMM_A_SPLIT | COFI_GEMM_L2NORM | COFI_GEMM_F16X3 | COFI_GEMM_W_F16PRE);
-    if (wf16 && (!f16 || wsplit)) return COFI_EINVAL;
-    if (l2n && (N > 128 || asplit)) return COFI_EUNSUPPORTED;
-    if (act < 0 || act > 3 || (wsplit && (bf16x3 == 0 || (ldw & 7))) || frames <= 0) return COFI_EINVAL;
-    if (asplit && bf16x3 != 1) return COFI_EINVAL;
-    if (asplit && (!wsplit || a_norm || (lda & 7) || (K & 7))) return COFI_EINVAL;
+    PlanRequest rq = gemm_request(M, N, K, act, a_norm ? 1 : 0, frames, ws ? ws_bytes : 0);
     const int sshift = colpart ? stat_shift_of(stat_width, N) : 0;
-    if (sshift < 0) return COFI_EINVAL;
-    Plan p = (asplit && g_force_pcfg != -2) ? make_planes_plan(M, N, K) : make_plan(M, N, K, l2n != 0, bf16x3);
-    if (bf16x3 == 2 && !wsplit && !asplit && !l2n && !(a_norm && frames > 1 && (M / frames) % 256)) big_plan(M, N, K, p, f16 != 0);   // the 256 x 128 kernel for the large shapes
-    if (a_norm && frames > 1 && p.pcfg < 0 && p.bm == 128 && p.bn == 64 && (M / frames) % 128) p.bm = 64;   // a normalising tile stays inside one frame
-    if (p.ksplit > 1 && (!ws || ws_bytes < (size_t)p.ksplit * M * N * sizeof(float))) return COFI_EWORKSPACE;
+    rq.operands_ok = sshift >= 0 && !(rq.wsplit && (ldw & 7)) && !(rq.asplit && (lda & 7));   // pre-split planes: rows of 8 values
     GemmArgs g{};
+    if (a_norm && frames > 0) rq.norm_status = norm_status(g, a_norm, K, M / frames, frames);
+    Plan p;
+    if (int rc = plan_gemm(rq, p)) return rc;
     g.A = A; g.W = W; g.C = C; g.bias = bias; g.rowdiv = rowdiv; g.ws = (float *)ws; g.colpart = colpart;
-    g.lda = lda; g.ldw = ldw; g.ldc = ldc; g.M = M; g.N = N; g.K = K; g.act = act; g.ksplit = 1;
-    g.bf16x3 = bf16x3; g.wsplit = wsplit; g.w_lo_off = (long)N * ldw; g.cv_Pout = 1; g.stat_shift = sshift;
-    g.asplit = asplit; g.a_lo_off = (long)M * lda;
-    g.l2n = l2n;
+    g.lda = lda; g.ldw = ldw; g.ldc = ldc; g.M = M; g.N = N; g.K = K; g.act = rq.act; g.ksplit = 1;
+    g.bf16x3 = rq.arith; g.wsplit = rq.wsplit; g.w_lo_off = (long)N * ldw; g.cv_Pout = 1; g.stat_shift = sshift;
+    g.asplit = rq.asplit; g.a_lo_off = (long)M * lda;
+    g.l2n = rq.l2n;
     g.res = res; g.ldr = ldr;
     if (res_idx) { g.res_idx = res_idx; g.res_idx_stride = res_idx_stride; g.res_rows = res_rows; g.res_out_rows = M / frames; }
-    if (f16 && p.big && wf16 && f16_two_per_cu(M, N, K, p)) p.bm = 128;
-    if (f16 && p.big) {   // the tile flags live behind this plan's split-K partials; a workspace without room for them: the six-product kernel
-        const size_t off = p.ksplit > 1 ? (size_t)p.ksplit * M * N * sizeof(float) : 0;
-        if (ws && ws_bytes >= off + f16_flag_bytes(M, N, p.ksplit)) {
-            g.f16 = 1;
-            g.fixflags = reinterpret_cast<unsigned *>(static_cast<char *>(ws) + off);
-        }
-    }
-    if (wf16) {   // a pre-split W is readable by gemm_f16_big_kernel only: the caller asks cofi_gemm_f16x3_eligible first
-        if (!g.f16) return COFI_EUNSUPPORTED;
-        g.wscale = W + (size_t)N * ldw;
-    }
-    if (int rc = set_a_norm(g, a_norm, K, M / frames, frames, p)) return rc;
+    if (a_norm) g.an_rows = M / frames;
+    set_f16_args(g, rq, p, ws, W, ldw);
     return launch(g, p, cofi_s(stream));
 }
 
 int conv_entry(const float *x, int ldx, const cofi_norm_desc_t *x_norm, int H, int W, int Cin, const float *Wt, int Cout, int ks, int stride,
                int pad, const float *bias, const float *res, int ldr, int act, int act_col0, float *y, int ldy, float *colpart, int stat_width,
                void *ws, size_t ws_bytes, int frames, cofi_stream_t stream) {
-    if (!x || !Wt || !y || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || (ks != 1 && ks != 3) || stride <= 0 || pad < 0) return COFI_EINVAL;
+    if (!x || !Wt || !y || act_col0 < 0 || act_col0 > Cout) return COFI_EINVAL;
     if ((Cin & 3) || (ldx & 3) || ldx < Cin || ldy < Cout || (res && ldr < Cout) || ((uintptr_t)x & 15) || ((uintptr_t)Wt & 15)) return COFI_EINVAL;
-    const int Ho = (H + 2 * pad - ks) / stride + 1, Wo = (W + 2 * pad - ks) / stride + 1;
-    if (frames <= 0) return COFI_EINVAL;
-    const int M = Ho * Wo * frames, K = ks * ks * Cin;
-    const int bf16x3 = (act & COFI_GEMM_BF16X6) ? 2 : ((act & COFI_GEMM_BF16X3) ? 1 : 0);
-    const int wsplit = (act & COFI_GEMM_W_SPLIT) ? 1 : 0;
-    const int l2n = (act & COFI_GEMM_L2NORM) ? 1 : 0;
-    const int f16 = (act & COFI_GEMM_F16X3) ? 1 : 0;
-    const int wf16 = (act & COFI_GEMM_W_F16PRE) ? 1 : 0;
-    act &= ~(COFI_GEMM_BF16X3 | COFI_GEMM_BF16X6 | COFI_GEMM_W_SPLIT | COFI_GEMM_L2NORM | COFI_GEMM_F16X3 | COFI_GEMM_W_F16PRE);
-    if (wf16 && (!f16 || wsplit)) return COFI_EINVAL;
-    if (act < 0 || act > 3 || (wsplit && bf16x3 == 0) || act_col0 < 0 || act_col0 > Cout) return COFI_EINVAL;
-    if (l2n && Cout > 128) return COFI_EUNSUPPORTED;
+    PlanRequest rq = conv_request(H, W, Cin, Cout, ks, stride, pad, ldx, act, x_norm ? (x_norm->scale_shift ? 2 : 1) : 0, frames, ws ? ws_bytes : 0);
     const int sshift = colpart ? stat_shift_of(stat_width, Cout) : 0;
-    if (sshift < 0) return COFI_EINVAL;
-    const int ldw = wsplit ? (K + 7) / 8 * 8 : K;   // pre-split planes: rows padded to 8 values
-    // narrow 3 x 3 convolutions of a stack-mode batch: the direct kernel (conv_direct.inc: input halo split once, 9 taps read it shifted)
-    {
-        static const int direct_env = getenv("COFI_CONV_DIRECT") ? atoi(getenv("COFI_CONV_DIRECT")) : 1;   // A/B switch: 0 = never
-        const int mode = g_force_direct ? g_force_direct : (direct_env ? 0 : -1);
-        const long tiles4 = (long)frames * (H / 4) * (W / 64);
-        const int th = (tiles4 >= 768 || g_force_direct == 2) ? 4 : 2;   // 4-row tiles once they fill the chip's workgroup slots (2 per CU) one and a half times
-        const long tiles = (long)frames * (H / th) * (W / 64);
-        const bool ok = bf16x3 == 2 && !wsplit && !l2n && ks == 3 && stride == 1 && pad == 1 && Cout == 64 && (Cin % 16) == 0 && Cin <= 512 && (W % 64) == 0 &&
-                        (H % 4) == 0 && (!x_norm || x_norm->scale_shift) && (size_t)frames * H * W * ldx * sizeof(float) < 0xffffffffull &&
-                        (size_t)Cout * K * sizeof(float) < 0xffffffffull;
-        if (ok && !wf16 && mode >= 0 && (mode > 0 || tiles >= 256) && !g_force_bm) {
-            GemmArgs g{};
-            g.A = x; g.W = Wt; g.C = y; g.bias = bias; g.colpart = colpart; g.res = res;
-            g.lda = ldx; g.ldw = K; g.ldc = ldy; g.ldr = ldr; g.M = M; g.N = Cout; g.K = K; g.act = act; g.ksplit = 1;
-            g.bf16x3 = 2;
-            g.cv_ks = 3; g.cv_H = H; g.cv_W = W; g.cv_Cin = Cin; g.cv_Wo = Wo; g.cv_stride = 1; g.cv_pad = 1; g.cv_Pout = Ho * Wo;
-            g.stat_shift = sshift;
-            g.act_col0 = act_col0;
-            Plan dp{};
-            dp.bm = 64; dp.bn = 64; dp.ksplit = 1; dp.pcfg = -1;
-            if (int rc = set_a_norm(g, x_norm, Cin, H * W, frames, dp)) return rc;
-            const dim3 grid(Cout / 64, (unsigned)tiles);
-            if (th == 4) {
-                if (g.an.part) hipLaunchKernelGGL((conv3x3_direct_kernel<true, 4>), grid, dim3(256), 0, cofi_s(stream), g);
-                else hipLaunchKernelGGL((conv3x3_direct_kernel<false, 4>), grid, dim3(256), 0, cofi_s(stream), g);
-            } else {
-                if (g.an.part) hipLaunchKernelGGL((conv3x3_direct_kernel<true, 2>), grid, dim3(256), 0, cofi_s(stream), g);
-                else hipLaunchKernelGGL((conv3x3_direct_kernel<false, 2>), grid, dim3(256), 0, cofi_s(stream), g);
-            }
-            return cofi_launch_status();
-        }
-    }
-    Plan p = make_plan(M, Cout, K, l2n != 0, bf16x3);
-    // the 256 x 128 kernel: 3 x 3 / stride 1 / pad <= 1 convolutions whose K-tiles of 32 lie inside one tap, 32-bit byte offsets into the input
-    if (bf16x3 == 2 && !wsplit && !l2n && ks == 3 && stride == 1 && pad <= 1 && (Cin % 32) == 0 &&
-        (size_t)frames * H * W * ldx * sizeof(float) < 0xffffffffull && !(x_norm && frames > 1 && (Ho * Wo) % 256))
-        big_plan(M, Cout, K, p, f16 != 0);
-    if (x_norm && frames > 1 && p.bm == 128 && p.bn == 64 && (Ho * Wo) % 128) p.bm = 64;   // a normalising tile stays inside one frame
-    if (p.ksplit > 1 && (!ws || ws_bytes < (size_t)p.ksplit * M * Cout * sizeof(float))) return COFI_EWORKSPACE;
+    rq.operands_ok = sshift >= 0;
     GemmArgs g{};
+    if (x_norm && frames > 0) rq.norm_status = norm_status(g, x_norm, Cin, H * W, frames);   // statistics of the INPUT map: H * W rows per frame
+    Plan p;
+    if (int rc = plan_conv(rq, p)) return rc;
+    const int M = rq.M, K = rq.K;
+    const int ldw = rq.wsplit ? (K + 7) / 8 * 8 : K;   // pre-split planes: rows padded to 8 values
     g.A = x; g.W = Wt; g.C = y; g.bias = bias; g.ws = (float *)ws; g.colpart = colpart; g.res = res;
-    g.lda = ldx; g.ldw = ldw; g.ldc = ldy; g.ldr = ldr; g.M = M; g.N = Cout; g.K = K; g.act = act; g.ksplit = 1;
-    g.bf16x3 = bf16x3; g.wsplit = wsplit; g.w_lo_off = (long)Cout * ldw;
-    g.cv_ks = ks; g.cv_H = H; g.cv_W = W; g.cv_Cin = Cin; g.cv_Wo = Wo; g.cv_stride = stride; g.cv_pad = pad; g.cv_Pout = Ho * Wo;
+    g.lda = ldx; g.ldw = ldw; g.ldc = ldy; g.ldr = ldr; g.M = M; g.N = Cout; g.K = K; g.act = rq.act; g.ksplit = 1;
+    g.bf16x3 = rq.arith; g.wsplit = rq.wsplit; g.w_lo_off = (long)Cout * ldw;
+    g.cv_ks = ks; g.cv_H = H; g.cv_W = W; g.cv_Cin = Cin; g.cv_Wo = conv_out_size(W, rq); g.cv_stride = stride; g.cv_pad = pad; g.cv_Pout = M / frames;
     g.stat_shift = sshift;
     g.act_col0 = act_col0;
-    g.l2n = l2n;
-    if (f16 && p.big && wf16 && f16_two_per_cu(M, Cout, K, p)) p.bm = 128;
-    if (f16 && p.big) {
-        const size_t off = p.ksplit > 1 ? (size_t)p.ksplit * M * Cout * sizeof(float) : 0;
-        if (ws && ws_bytes >= off + f16_flag_bytes(M, Cout, p.ksplit)) {
-            g.f16 = 1;
-            g.fixflags = reinterpret_cast<unsigned *>(static_cast<char *>(ws) + off);
-        }
-    }
-    if (wf16) {
-        if (!g.f16) return COFI_EUNSUPPORTED;
-        g.wscale = Wt + (size_t)Cout * ldw;
-    }
-    if (int rc = set_a_norm(g, x_norm, Cin, H * W, frames, p)) return rc;   // statistics of the INPUT map: H * W rows per frame
+    g.l2n = rq.l2n;
+    if (x_norm) g.an_rows = M / frames;
+    set_f16_args(g, rq, p, ws, Wt, ldw);
     return launch(g, p, cofi_s(stream));
+}
+
+int describe(int rc, const Plan &p, cofi_plan_desc_t *out) {
+    *out = cofi_plan_desc_t{};
+    out->status = rc;
+    if (rc) return rc;
+    out->family = p.family;
+    out->bm = p.bm; out->bn = p.bn; out->ksplit = p.ksplit; out->kchunk = p.kchunk; out->pcfg = p.pcfg;
+    out->partial_bytes = (long long)p.partial_bytes;
+    out->flag_offset = p.flag_off;
+    out->ws_bytes = (long long)p.ws_bytes;
+    return 0;
 }
 
 }  // namespace
 
 // Would a COFI_GEMM_BF16X6 | COFI_GEMM_F16X3 launch of this shape run on gemm_f16_big_kernel (with a workspace of cofi_gemm_f32_workspace bytes)?
-// The conditions of gemm_entry / conv_entry, restated: a caller holding a pre-split W (COFI_GEMM_W_F16PRE) asks before it passes it.
+// The planner's answer for that request: a caller holding a pre-split W (COFI_GEMM_W_F16PRE) asks before it passes it.
 extern "C" int cofi_gemm_f16x3_eligible(int M, int N, int K, int pending_norm, int frames) {
     if (M <= 0 || N <= 0 || K <= 0 || frames <= 0) return 0;
-    if (pending_norm && frames > 1 && (M / frames) % 256) return 0;
-    Plan p = make_plan(M, N, K, false, 2);
-    return big_plan(M, N, K, p, true) ? 1 : 0;
+    Plan p;
+    return plan_gemm(gemm_request(M, N, K, COFI_GEMM_BF16X6 | COFI_GEMM_F16X3, pending_norm ? 1 : 0, frames, cofi_gemm_f32_workspace(M, N, K)), p) == 0 &&
+           plan_is_f16x3(p);
 }
 
 extern "C" int cofi_conv2d_f16x3_eligible(int H, int W, int Cin, int Cout, int ks, int stride, int pad, int ldx, int pending_norm, int frames) {
-    if (H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || stride <= 0 || pad < 0 || frames <= 0 || (ks != 1 && ks != 3)) return 0;
-    const int Ho = (H + 2 * pad - ks) / stride + 1, Wo = (W + 2 * pad - ks) / stride + 1;
-    const int M = Ho * Wo * frames, K = ks * ks * Cin;
-    if (!(ks == 3 && stride == 1 && pad <= 1 && (Cin % 32) == 0 && (size_t)frames * H * W * ldx * sizeof(float) < 0xffffffffull)) return 0;
-    if (pending_norm && frames > 1 && (Ho * Wo) % 256) return 0;
-    Plan p = make_plan(M, Cout, K, false, 2);
-    return big_plan(M, Cout, K, p, true) ? 1 : 0;
+    PlanRequest r = conv_request(H, W, Cin, Cout, ks, stride, pad, ldx, COFI_GEMM_BF16X6 | COFI_GEMM_F16X3, pending_norm ? 1 : 0, frames, 0);
+    if (!conv_contraction(r)) return 0;
+    r.ws_bytes = cofi_gemm_f32_workspace(r.M, r.N, r.K);
+    Plan p;
+    return plan_conv(r, p) == 0 && plan_is_f16x3(p);
 }
 
+// The most any plan of (M, N, K) uses, over the operand forms a caller can pass: fp32 / bf16x3, both operands pre-split, bf16x6 with
+// pre-split and with fp32 weights (the 256 x 128 kernel's shapes), f16x3 (its own table of shapes and splits, and its tile flags)
 extern "C" size_t cofi_gemm_f32_workspace(int M, int N, int K) {
     if (M <= 0 || N <= 0 || K <= 0) return 0;
-    const Plan p = make_plan(M, N, K, false), q = make_planes_plan(M, N, K), r = make_plan(M, N, K, false, 2);   // whichever kernel the operands select
-    Plan b = r, bf = r;
-    big_plan(M, N, K, b);                            // the six-product 256 x 128 kernel's plan ...
-    const bool bigf = big_plan(M, N, K, bf, true);   // ... and the f16x3 kernel's (its own table of shapes and splits)
-    const int ks = std::max(std::max(p.ksplit, b.ksplit), std::max(std::max(q.ksplit, r.ksplit), bf.ksplit));
-    // split-K partials, then (shapes of the f16x3 kernel) its tile flags behind the partials of THAT plan
-    const size_t partials = ks > 1 ? (size_t)ks * M * N * sizeof(float) : 0;
-    return bigf ? std::max(partials, (bf.ksplit > 1 ? (size_t)bf.ksplit * M * N * sizeof(float) : 0) + f16_flag_bytes(M, N, bf.ksplit)) : partials;
+    size_t need = 0;
+    for (const int form : {COFI_GEMM_BF16X3, COFI_GEMM_BF16X3 | COFI_GEMM_W_SPLIT | COFI_GEMM_A_SPLIT, COFI_GEMM_BF16X6 | COFI_GEMM_W_SPLIT,
+                           COFI_GEMM_BF16X6, COFI_GEMM_BF16X6 | COFI_GEMM_F16X3}) {
+        Plan p;
+        if (plan_gemm(gemm_request(M, N, K, form, 0, 1, SIZE_MAX), p) == 0) need = std::max(need, p.ws_bytes);
+    }
+    return need;
 }
 
 extern "C" int cofi_gemm_f32_stat_slabs(int M, int N, int K) {
@@ -1759,18 +1499,16 @@ extern "C" int cofi_gemm_f32_layernorm(const float *A, int lda, const float *W, 
                                        const float *bias, const float *gamma, const float *beta, float eps, int relu, const float *res,
                                        int ldr, void *ws, size_t ws_bytes, cofi_stream_t stream) {
     if (int rc = check_common(A, lda, W, ldw, C, ldc, M, N, K)) return rc;
-    if (!gamma || !beta || N > 128 || (res && ldr < N)) return COFI_EINVAL;
+    if (!gamma || !beta || N > 128 || (res && ldr < N)) return COFI_EINVAL;   // (N: refused for an empty problem too, which is never planned)
     if (M == 0) return 0;
-    const int bf16x3 = (relu & COFI_GEMM_BF16X6) ? 2 : ((relu & COFI_GEMM_BF16X3) ? 1 : 0);
-    Plan p = make_plan(M, N, K, true, bf16x3);
-    if (p.ksplit > 1 && (!ws || ws_bytes < (size_t)p.ksplit * M * N * sizeof(float))) return COFI_EWORKSPACE;
-    const int wsplit = (relu & COFI_GEMM_W_SPLIT) ? 1 : 0;
-    relu &= ~(COFI_GEMM_BF16X3 | COFI_GEMM_BF16X6 | COFI_GEMM_W_SPLIT | COFI_GEMM_F16X3);   // the fused LayerNorm never takes the 256 x 128 kernel
-    if (wsplit && (bf16x3 == 0 || (ldw & 7))) return COFI_EINVAL;
+    PlanRequest rq = layernorm_request(M, N, K, relu, ws ? ws_bytes : 0);
+    rq.operands_ok = !(rq.wsplit && (ldw & 7));
+    Plan p;
+    if (int rc = plan_gemm(rq, p)) return rc;
     GemmArgs g{};
     g.A = A; g.W = W; g.C = C; g.bias = bias; g.ws = (float *)ws; g.ln_gamma = gamma; g.ln_beta = beta; g.res = res;
-    g.lda = lda; g.ldw = ldw; g.ldc = ldc; g.ldr = ldr; g.M = M; g.N = N; g.K = K; g.ksplit = 1; g.ln_relu = relu; g.ln_eps = eps;
-    g.bf16x3 = bf16x3; g.wsplit = wsplit; g.w_lo_off = (long)N * ldw; g.cv_Pout = 1;
+    g.lda = lda; g.ldw = ldw; g.ldc = ldc; g.ldr = ldr; g.M = M; g.N = N; g.K = K; g.ksplit = 1; g.ln_relu = rq.act; g.ln_eps = eps;
+    g.bf16x3 = rq.arith; g.wsplit = rq.wsplit; g.w_lo_off = (long)N * ldw; g.cv_Pout = 1;
     return launch(g, p, cofi_s(stream));
 }
 
@@ -1847,4 +1585,19 @@ extern "C" int cofi_tune_force_plan(int bm, int bn, int ksplit) {
     if (!ok || ksplit < 0) return COFI_EINVAL;
     g_force_bm = bm; g_force_bn = bn; g_force_ks = ksplit;
     return 0;
+}
+
+// The planner's answer for a request, under the calling thread's overrides; nothing is launched (no GPU needed).
+extern "C" int cofi_tune_describe_gemm(int M, int N, int K, int act, int fused_ln, int pending_norm, int frames, size_t ws_bytes, cofi_plan_desc_t *out) {
+    if (!out) return COFI_EINVAL;
+    Plan p{};
+    return describe(plan_gemm(fused_ln ? layernorm_request(M, N, K, act, ws_bytes) : gemm_request(M, N, K, act, pending_norm, frames, ws_bytes), p), p, out);
+}
+
+extern "C" int cofi_tune_describe_conv(int H, int W, int Cin, int Cout, int ks, int stride, int pad, int ldx, int act, int pending_norm, int frames,
+                                       size_t ws_bytes, cofi_plan_desc_t *out) {
+    if (!out) return COFI_EINVAL;
+    PlanRequest r = conv_request(H, W, Cin, Cout, ks, stride, pad, ldx, act, pending_norm, frames, ws_bytes);
+    Plan p{};
+    return describe(plan_conv(r, p), p, out);
 }
