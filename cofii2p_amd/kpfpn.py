@@ -41,6 +41,8 @@ DECODER_PROJECT_MIN_ROWS = {"decoder3": 16384}
 # spread on two of three layers - and the wide layers' kernel stages through NP waves and has no sorted form: those keep the unsorted
 # kernels and are not charged the launch that writes the flag bits.
 PREFIX_MAX_CHANNELS = 64
+# this module's part of the key of every recording (ops.ROUTING)
+ROUTING = ("FUSED_KPCONV", "AGG_PLANES", "AGG_PLANES_MIN_FRAMES", "DECODER_CONCAT", "DECODER_PROJECT_MIN_ROWS", "PREFIX_MAX_CHANNELS")
 
 
 def decoder_weight_unused(key: str) -> bool:

@@ -9,13 +9,15 @@ the differentiable form of the same network (train_forward.py: HIP kernels forwa
 raises if the HIP library is missing or a tensor is not on the GPU.
 """
 import os
-from typing import Dict, List, Optional
+import sys
+from typing import Dict, NamedTuple, Optional
 
 import numpy as np
 import torch
 import torch.nn as nn
 
 from . import _lib, image, kpfpn, ops, transformer
+from . import pose as _pose
 from .spec import D_MODEL, LAYER_KINDS, N_HEAD, N_LAYERS, is_buffer, state_dict_spec
 
 __all__ = ["CoFiI2P", "CoFiI2P_wrapper", "fine_process", "extract_patch", "point2node", "square_distance", "fine_matching",
@@ -51,6 +53,82 @@ def score_thresholds(n: int = 64) -> np.ndarray:
 
 
 ALTERNATE_ORDER = True   # odd forward_async slots run the point encoder first (measured 515-518 vs 510 frames/s)
+ROUTING = ("ALTERNATE_ORDER",)   # this module's part of the key of every recording (ops.ROUTING)
+
+
+def routing_state() -> tuple:
+    """The current value of every switch that decides which kernels a forward enqueues (the ROUTING tuples of ops, kpfpn, transformer and
+    this module), as one hashable tuple: part of the key of every recording (CoFiI2P._graph_forward, train_step.GraphedTrainStep), so
+    that a switch flipped inside a process records anew instead of replaying the old launch sequence.  Read afresh on every call (a
+    cached value would be as stale as the recordings it guards).  Not in here: the `static const` getenv switches of
+    csrc/gemm_planner.h, which are fixed for the life of the process."""
+    state = []
+    for module in (ops, kpfpn, transformer, sys.modules[__name__]):
+        for name in module.ROUTING:
+            v = getattr(module, name)
+            if callable(v):
+                v = v()
+            state.append(tuple(sorted(v.items())) if isinstance(v, dict) else v)
+    return tuple(state)
+
+
+def _as_idx32(t: torch.Tensor) -> torch.Tensor:
+    return ops.idx_to_int32(t) if t.dtype != torch.int32 else t.contiguous()
+
+
+class ForwardInputs(NamedTuple):
+    """The inputs of one device-side forward, prepared once: contiguous tensors, int32 index tables.  `order` is a list (empty when the
+    pyramid has none), `kpt` / `inl` the labels of mode 'train' / 'val' or None."""
+    points: list
+    neighbors: list
+    subsampling: list
+    upsampling: list
+    order: list
+    feats: torch.Tensor
+    img: torch.Tensor
+    kpt: Optional[torch.Tensor]
+    inl: Optional[torch.Tensor]
+    sorted_tables: bool
+
+    @classmethod
+    def prepare(cls, pc_data_dict, img, labels=(None, None), inputs_stable: bool = False):
+        """inputs_stable: the recording reads these very tensors, so nothing may need a copy or a conversion"""
+        if inputs_stable:
+            for k in ("points", "neighbors", "subsampling", "upsampling"):
+                for t in pc_data_dict[k]:
+                    if not t.is_contiguous() or (k != "points" and t.dtype != torch.int32):
+                        raise _lib.CofiError("inputs_stable=True reads the inputs in place: contiguous tensors and int32 tables only (%s)" % k)
+            if not (pc_data_dict["feats"].is_contiguous() and img.is_contiguous()):
+                raise _lib.CofiError("inputs_stable=True reads the inputs in place: contiguous feats / img only")
+        tabs = [[_as_idx32(t) for t in pc_data_dict[k]] for k in ("neighbors", "subsampling", "upsampling")]
+        return cls([p.contiguous() for p in pc_data_dict["points"]], *tabs, list(pc_data_dict.get("order") or []),
+                   pc_data_dict["feats"].contiguous(), img.contiguous(), labels[0], labels[1], bool(pc_data_dict.get("sorted_tables")))
+
+    def flat(self) -> list:
+        """every tensor of the record (absent labels as None), in field order"""
+        return [*self.points, *self.neighbors, *self.subsampling, *self.upsampling, *self.order, self.feats, self.img, self.kpt, self.inl]
+
+    def rebuild(self, flat):
+        """a record of this one's structure over the tensors of another flat list (a recording's static buffers)"""
+        it = iter(flat)
+        lists = [[next(it) for _ in field] for field in self[:5]]
+        return ForwardInputs(*lists, *it, self.sorted_tables)
+
+
+class _Recording(NamedTuple):
+    """one entry of CoFiI2P._graphs"""
+    graph: "torch.cuda.CUDAGraph"
+    inputs: ForwardInputs          # the tensors the graph reads: the caller's own (inputs_stable) or static buffers
+    outs: list
+    copy: Optional[ops.MultiCopy]  # inputs of a submission -> the static buffers, one launch (None: inputs_stable)
+
+
+class _Slot:
+    """what a forward_async slot owns on one device next to its recordings (a slot is finished before it is reused)"""
+
+    def __init__(self):
+        self.count_host = {}   # frames of a submission -> the pinned landing buffer of their match counts
+        self.pose = _pose.PoseTail()
 
 
 _EXTRA_FRAME_STREAMS = {}   # device -> streams handed out by CoFiI2P.frame_streams beyond the capture and the default stream
@@ -112,8 +190,9 @@ class CoFiI2P(nn.Module):
         self.compute_unused_image_maps = os.environ.get("COFI_DEAD_MAPS", "1") != "0"  # layer3/layer4/avg-pool of the ResNet (network.py:87-89): read by nothing
         self._use_graphs = False
         self._auto_graphs = bool(self.DEFAULT_GRAPHS)
-        self._graphs = {}
-        self._multicopy = {}
+        self._graphs = {}    # key (see _graph_forward) -> _Recording
+        self._slots = {}     # (slot, device) -> _Slot
+        self._capture = None   # the stream recordings are warmed up and captured on (_capture_stream)
         self._grid_cache = {}
 
         # intra-frame fork/join slots captured by forward_async (bit 0 image branch, 1 residual shortcuts, 2 attention streams,
@@ -123,13 +202,17 @@ class CoFiI2P(nn.Module):
         self.eval()
 
     # ------------------------------------------------------------------ weights
-    def _invalidate(self):
-        self._packed = None
+    def _drop_recordings(self):
+        """every recording, with its static inputs, its outputs and its staging copy; the slots' own buffers (pinned counts, pose tails)
+        depend on neither the weights nor a recording and stay"""
         self._graphs = {}
 
-    def _apply(self, fn, *a, **k):
+    def _invalidate(self):
         self._packed = None
-        self._graphs = {}
+        self._drop_recordings()
+
+    def _apply(self, fn, *a, **k):
+        self._invalidate()
         return super()._apply(fn, *a, **k)
 
     def _param_versions(self) -> int:
@@ -143,7 +226,7 @@ class CoFiI2P(nn.Module):
         if self._packed is not None and self._packed_key == stamp:
             return self._packed
         if self._packed is not None:
-            self._graphs = {}
+            self._drop_recordings()
         sd = {k: v.detach() for k, v in self.state_dict().items()}
         for k, v in sd.items():
             if v.device != device:
@@ -183,9 +266,7 @@ class CoFiI2P(nn.Module):
             g = self._grid_cache[key] = torch.stack([gy, gx], -1).reshape(H8 * W8, 2).repeat(B, 1).contiguous()
         return g
 
-    @staticmethod
-    def _as_idx32(t: torch.Tensor) -> torch.Tensor:
-        return ops.idx_to_int32(t) if t.dtype != torch.int32 else t.contiguous()
+    _as_idx32 = staticmethod(_as_idx32)
 
     def _score_head(self, P, head: str, tokens: torch.Tensor, frames: int = 1) -> torch.Tensor:
         """network.py:42-43 on token-major data: 1x1 conv = GEMM, InstanceNorm over positions = per-column
@@ -381,12 +462,17 @@ class CoFiI2P(nn.Module):
         self._use_graphs = bool(flag)
         if not flag:
             self._auto_graphs = False
-            self._graphs = {}
-            self._multicopy = {}
+            self._drop_recordings()
         return self
 
-    def _graph_forward(self, P, points, neighbors, subsampling, upsampling, feats, img, mode, kpt, inl, slot: int = 0,
-                       branch_mask: int = 7, order=None, inputs_stable: bool = False, cameras: int = 1, sorted_tables: bool = False):
+    def _capture_stream(self, dev) -> "torch.cuda.Stream":
+        """the capture stream of this device: recordings are warmed up AND captured on it, frame_streams hands it out first"""
+        if self._capture is None or self._capture.device != dev:
+            self._capture = torch.cuda.Stream(device=dev)
+        return self._capture
+
+    def _graph_forward(self, P, inputs: ForwardInputs, mode, slot: int = 0, branch_mask: int = 7, inputs_stable: bool = False,
+                       cameras: int = 1):
         def sig(t):
             if t is None:
                 return None
@@ -396,65 +482,48 @@ class CoFiI2P(nn.Module):
                 return (tuple(t.shape), str(t.dtype), t.data_ptr())
             return (tuple(t.shape), str(t.dtype))
 
-        order = [] if order is None else list(order)
-        tensors = list(points) + list(neighbors) + list(subsampling) + list(upsampling) + order + [feats, img, kpt, inl]
-        # everything a captured launch sequence depends on besides the tensor signature: arithmetic, optional branches
-        key = ("stable" if inputs_stable else "copy", mode, str(img.device), slot, branch_mask, ops.gemm_mode(), ops.f16x3_big(), self.compute_unused_image_maps,
-               transformer.JOINT_SELF, transformer.FUSED_CHAIN, transformer.TAIL_MAX_ROWS, kpfpn.FUSED_KPCONV, kpfpn.AGG_PLANES, cameras,
-               bool(sorted_tables) and ops.kpconv_prefix()) + tuple(sig(t) for t in tensors)
-        saved_mask, saved_slot = ops.BRANCH_MASK, ops.Workspace.slot
-        ops.set_workspace_slot(slot)
-        ops.BRANCH_MASK = branch_mask  # which intra-frame forks the capture records
-        try:
-            ent = self._graphs.get(key)
-            if ent is None:
+        tensors, dev = inputs.flat(), inputs.img.device
+        # what the call itself fixes of the launch sequence, then every switch (routing_state), then the tensor signatures
+        key = ("stable" if inputs_stable else "copy", mode, str(dev), slot, branch_mask, cameras, inputs.sorted_tables,
+               self.compute_unused_image_maps) + routing_state() + tuple(sig(t) for t in tensors)
+        with ops.recording_scope(slot, branch_mask):   # the slot's scratch namespace; which intra-frame forks the capture records
+            rec = self._graphs.get(key)
+            if rec is None:
                 if inputs_stable:
                     if sum(1 for k_ in self._graphs if k_[0] == "stable") >= self.MAX_STABLE_GRAPHS:
                         raise _lib.CofiError("inputs_stable=True: more than %d distinct input sets; recycle the input buffers or pass "
                                              "inputs_stable=False" % self.MAX_STABLE_GRAPHS)
-                    static = list(tensors)   # the entry keeps the tensors alive for as long as the graph exists
+                    static = inputs   # the entry keeps the tensors alive for as long as the graph exists
                 else:
                     copies = [k_ for k_ in self._graphs if k_[0] == "copy"]
                     if len(copies) >= self.MAX_COPY_GRAPHS:   # a caller whose frames keep changing size: bounded memory, oldest signature first
                         del self._graphs[copies[0]]
-                        self._multicopy.pop(copies[0], None)
-                    static = [None if t is None else torch.empty_like(t) for t in tensors]
-                    for s_, t in zip(static, tensors):
-                        if t is not None:
-                            s_.copy_(t)
-                n = [len(points), len(neighbors), len(subsampling), len(upsampling), len(order)]
-                o = [0, n[0], n[0] + n[1], n[0] + n[1] + n[2], n[0] + n[1] + n[2] + n[3], sum(n)]
-                args = (static[o[0]:o[1]], static[o[1]:o[2]], static[o[2]:o[3]], static[o[3]:o[4]], static[o[5]], static[o[5] + 1], mode,
-                        static[o[5] + 2], static[o[5] + 3], None, (static[o[4]:o[5]] or None),
-                        ALTERNATE_ORDER and branch_mask == 0 and bool(slot & 1), cameras, bool(sorted_tables))
+                    static = inputs.rebuild([None if t is None else torch.empty_like(t).copy_(t) for t in tensors])
+
+                def run():
+                    return self._run_device(P, static.points, static.neighbors, static.subsampling, static.upsampling, static.feats, static.img,
+                                            mode, static.kpt, static.inl, taps=None, order=static.order or None,
+                                            pc_first=ALTERNATE_ORDER and branch_mask == 0 and bool(slot & 1), cameras=cameras,
+                                            sorted_tables=static.sorted_tables)
+
                 # warm-up AND capture run on one persistent stream, so every per-stream workspace is grown (in the
                 # ordinary allocator pool) before the capture starts and nothing is allocated for it inside
-                if getattr(self, "_capture_stream", None) is None or self._capture_stream.device != img.device:
-                    self._capture_stream = torch.cuda.Stream(device=img.device)
-                cap = self._capture_stream
+                cap = self._capture_stream(dev)
                 cap.wait_stream(torch.cuda.current_stream())
                 with torch.cuda.stream(cap):
                     for _ in range(2):
-                        self._run_device(P, *args)
+                        run()
                 torch.cuda.current_stream().wait_stream(cap)
                 torch.cuda.synchronize()
                 graph = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(graph, stream=cap):
-                    outs = self._run_device(P, *args)
-                ent = (graph, static, outs)
-                self._graphs[key] = ent
-            graph, static, outs = ent
-            if not inputs_stable:
+                    outs = run()
+                rec = self._graphs[key] = _Recording(graph, static, outs, None if inputs_stable else ops.MultiCopy(dev))
+            if rec.copy is not None:
                 # per-frame inputs -> the static buffers the graph reads: one batched copy launch (20+ tensors)
-                mc = self._multicopy.get(key)
-                if mc is None:
-                    mc = self._multicopy[key] = ops.MultiCopy(img.device)
-                mc.run([None if t is None else t.contiguous() for t in tensors], static)
-            graph.replay()
-        finally:   # an exception during warm-up / capture must not leave later eager forwards in this slot's scratch namespace
-            ops.set_workspace_slot(saved_slot)
-            ops.BRANCH_MASK = saved_mask
-        return outs
+                rec.copy.run([None if t is None else t.contiguous() for t in tensors], rec.inputs.flat())
+            rec.graph.replay()
+        return rec.outs
 
     # ------------------------------------------------------------------ frames in flight / stack-mode batches
     @staticmethod
@@ -485,9 +554,7 @@ class CoFiI2P(nn.Module):
         dev = torch.device(device) if device is not None else next(self.parameters()).device
         if dev.type == "cuda" and dev.index is None:
             dev = torch.device("cuda", torch.cuda.current_device())   # 'cuda' and 'cuda:0' are one pool
-        if getattr(self, "_capture_stream", None) is None or self._capture_stream.device != dev:
-            self._capture_stream = torch.cuda.Stream(device=dev)
-        pool = [self._capture_stream, torch.cuda.default_stream(dev)]
+        pool = [self._capture_stream(dev), torch.cuda.default_stream(dev)]
         # the extra streams are created once per device and process: HIP binds a stream to the least-loaded hardware queue when it is
         # created, so fresh streams per call would land on different queues from one call to the next (a pipeline with the KNN pyramid in
         # the chain measured 355 or 478 frames/s depending on that)
@@ -556,9 +623,8 @@ class CoFiI2P(nn.Module):
         pose on that image's own rows.  True estimates the pixel variance from the residuals.  Refused before anything is enqueued:
         pose_cov without pose_K, a pixel noise that is not a finite number > 0.  With the default False nothing about the call, its handle,
         its buffers or its launches changes."""
+        B = img.shape[0] if img.dim() == 4 else 1
         if pose_cov is not False and pose_cov is not None:
-            from . import pose as _pose
-
             if pose_K is None:
                 raise _lib.CofiError("forward_async(pose_cov=...): the covariance belongs to the pose tail - pass pose_K")
             pose_cov = (_pose._sigma(pose_cov) or None,)   # (None,): estimate the pixel variance
@@ -569,17 +635,14 @@ class CoFiI2P(nn.Module):
                 raise ValueError("a rig (cameras = %d > 1) serves mode='test' only, got mode=%r" % (cameras, mode))
             raise ValueError("forward_async serves the test-mode pipeline")
         _lib.load()
-        self._check_rig(pc_data_dict, img, cameras)
+        S = self._check_rig(pc_data_dict, B, cameras)
         if rig_extrinsics is not None:
-            from . import pose as _pose
-
             if pose_K is None:
                 raise _lib.CofiError("forward_async(rig_extrinsics=...): the rig pose is a pose tail - pass pose_K")
             if cameras == 1:
                 raise _lib.CofiError("forward_async(rig_extrinsics=...): a rig has cameras > 1; one camera is served by pose_K alone")
             if not isinstance(rig_extrinsics, tuple):   # checked (and converted) before anything is enqueued
                 rig_extrinsics = _pose.rig_extrinsics(rig_extrinsics, cameras, "cpu")
-            S = (img.shape[0] if img.dim() == 4 else 1) // cameras
             ext = rig_extrinsics[0]
             if not (torch.is_tensor(ext) and tuple(ext.shape) in ((cameras, 12), (S, cameras, 12))):
                 raise _lib.CofiError("forward_async(rig_extrinsics=...): need the extrinsics of C = %d cameras, shared or for each of S = %d rigs"
@@ -589,30 +652,51 @@ class CoFiI2P(nn.Module):
 
             if pose_K is None:
                 raise _lib.CofiError("forward_async(eval_into=...): the monitors read the submission's poses - pass pose_K")
-            evaluation.check_eval_into(eval_into, img.shape[0] if img.dim() == 4 else 1, img.device)
+            evaluation.check_eval_into(eval_into, B, img.device)
         if fuse_into is not None:
             from . import fusion
 
             if pose_K is None:
                 raise _lib.CofiError("forward_async(fuse_into=...): the fusion reads the submission's poses - pass pose_K")
-            B = img.shape[0] if img.dim() == 4 else 1
-            S, rows = B // cameras, pc_data_dict["points"][0].shape[0]
+            rows = pc_data_dict["points"][0].shape[0]
             want = (S, rows // S, B, img.shape[-2], img.shape[-1], img.shape[-3])
             if not isinstance(fuse_into, fusion.FusionBuffers) or rows % S or not fuse_into.fits(*want, img.device):
                 raise _lib.CofiError("forward_async(fuse_into=...): need a fusion.FusionBuffers made for (S, N, F, H, W, Ci) = %s on %s"
                                      % (want, img.device))
+        inputs = ForwardInputs.prepare(pc_data_dict, img, inputs_stable=inputs_stable)
+        # submissions in flight fill the GPU by themselves: the per-submission graph is a linear chain (intra-frame
+        # fork/join only adds join latency then — measured 254 vs 331 frames/s at two frames in flight)
         with ops.arithmetic(self.arithmetic):
-            return self._forward_async(slot, pc_data_dict, img, mode, inputs_stable, pose_K, pose_iterations, pose_seed, eval_into, cameras,
-                                       rig_extrinsics, fuse_into, pose_cov)
+            outs = self._graph_forward(self._pack(img.device), inputs, mode, slot=slot, branch_mask=self.async_branch_mask,
+                                       inputs_stable=inputs_stable, cameras=cameras)
+        own = self._slots.get((slot, str(img.device)))
+        if own is None:
+            own = self._slots[(slot, str(img.device))] = _Slot()
+        host = own.count_host.get(B)
+        if host is None:
+            host = own.count_host[B] = torch.empty((B, 2), dtype=torch.int32, pin_memory=True)
+        host.copy_(outs[0]["count_all"], non_blocking=True)
+        pose = rig_pose = None
+        if pose_K is not None:
+            pose, K_dev, rig_pose = own.pose.enqueue(outs, pose_K, pose_iterations, pose_seed, cameras, rig_extrinsics, pose_cov)
+        if eval_into is not None:   # the evaluation monitors of the submission: one launch behind the pose tail
+            evaluation.eval_monitors({"out": outs, "pose": pose}, K_dev, eval_into[1], eval_into[0], eval_into[2])
+        if fuse_into is not None:   # the registered cloud of the submission: four launches behind the pose tail
+            im = inputs.img.reshape((-1,) + tuple(img.shape[-3:]))
+            fusion.fuse_into(inputs.points[0], im, pose, K_dev, fuse_into, result=pose["result"], cameras=cameras,
+                             k_scale=float(im.shape[3]) / float(4 * (im.shape[3] // 8)))
+        handle = {"out": outs, "count_host": host, "done": torch.cuda.Event()}
+        handle["done"].record()
+        handle.update((k, v) for k, v in (("fusion", fuse_into), ("pose", pose), ("rig_pose", rig_pose)) if v is not None)
+        return handle
 
     @staticmethod
-    def _check_rig(pc_data_dict, img, cameras):
-        """the shape rules of a rig submission (cameras > 1), checked before anything is enqueued"""
+    def _check_rig(pc_data_dict, B, cameras) -> int:
+        """the shape rules of a rig submission (cameras > 1) of B images, checked before anything is enqueued -> S, its clouds"""
         if not isinstance(cameras, int) or cameras < 1:
             raise _lib.CofiError("forward_async: cameras must be an integer >= 1, got %r" % (cameras,))
         if cameras == 1:
-            return
-        B = img.shape[0] if img.dim() == 4 else 1
+            return B
         if B % cameras:
             raise _lib.CofiError("forward_async: B = %d images are no whole number of rigs of C = %d cameras" % (B, cameras))
         S = B // cameras
@@ -622,125 +706,7 @@ class CoFiI2P(nn.Module):
             if t.shape[0] % S:
                 raise _lib.CofiError("forward_async: B = %d images with C = %d cameras are S = %d clouds, which does not divide the %d rows of %s"
                                      % (B, cameras, S, t.shape[0], name))
-
-    @staticmethod
-    def _cov_bufs(holder, frames, dev):
-        """the covariance buffers a slot owns for `frames` bodies, made when a submission first asks for them"""
-        c = holder.get("cov")
-        if c is None:
-            c = holder["cov"] = {"cov": torch.empty((frames, 6, 6), dtype=torch.float64, device=dev),
-                                 "info": torch.empty((frames, 6, 6), dtype=torch.float64, device=dev),
-                                 "stat": torch.empty((frames, 4), dtype=torch.float64, device=dev)}
-        return c
-
-    def _enqueue_pose(self, slot, outs, K, iterations, seed, cameras=1, rig_ext=None, pose_cov=None):
-        """the batched pose tail of a submission (with rig_ext = (ext, rig stride): the rig solve; with pose_cov = (sigma_px or None,): the
-        covariance launch behind it), on the current stream, into buffers the slot owns -> (handle["pose"], K on the device,
-        handle["rig_pose"] or None)"""
-        from . import pose as _pose
-
-        if "coarse_pts_all" not in outs[0]:
-            raise _lib.CofiError("forward_async(pose_K=...): the batched pose tail reads the outputs of match_finish, which serves fine "
-                                 "feature maps of at most 128 channels; this model's fine map is wider")
-        cpts, fxy, cnt = outs[0]["coarse_pts_all"], outs[0]["fine_xy_all"], outs[0]["count_all"]
-        B, cap, dev = cpts.shape[0], cpts.shape[1], cpts.device
-        if not torch.is_tensor(K):
-            K = torch.as_tensor(np.asarray(K, dtype=np.float32))
-        if tuple(K.shape) not in ((B, 3, 3), (3, 3)):
-            raise _lib.CofiError("forward_async: pose_K must be (B,3,3) = %s or (3,3), got %s" % ((B, 3, 3), tuple(K.shape)))
-        bufs = self.__dict__.setdefault("_pose_bufs", {})
-        key = (slot, B, cap, int(iterations), str(dev))
-        b = bufs.get(key)
-        if b is None:
-            b = bufs[key] = {"ws": torch.empty(_pose.pnp_batch_workspace(iterations, B), dtype=torch.uint8, device=dev),
-                             "pose": torch.empty((B, 12), dtype=torch.float32, device=dev),
-                             "result": torch.empty((B, 3), dtype=torch.int32, device=dev),
-                             "mask": torch.empty((B, cap), dtype=torch.uint8, device=dev),
-                             "K": torch.empty((B, 3, 3), dtype=torch.float32, device=dev)}
-        if not (K.is_cuda and K.device == dev and K.dtype == torch.float32 and K.dim() == 3 and K.is_contiguous()):
-            b["K"].copy_(K, non_blocking=True)   # broadcasts a (3,3); a device K of another dtype is converted on the device
-            K = b["K"]
-        if rig_ext is not None:
-            S = B // cameras
-            ext, estride = rig_ext
-            r = b.get("rig")
-            if r is None:
-                r = b["rig"] = {"ws": torch.empty(_pose.pnp_rig_workspace(iterations, S), dtype=torch.uint8, device=dev),
-                                "pose": torch.empty((S, 12), dtype=torch.float32, device=dev),
-                                "result": torch.empty((S, 3), dtype=torch.int32, device=dev)}
-            if not (ext.is_cuda and ext.device == dev):   # a host set: into a buffer of the slot, as K
-                buf = r.get("ext")
-                if buf is None or buf.shape != ext.shape:
-                    buf = r["ext"] = torch.empty(tuple(ext.shape), dtype=torch.float32, device=dev)
-                buf.copy_(ext, non_blocking=True)
-                ext = buf
-            rig, per = _pose.solve_pnp_ransac_rig_into(cpts, fxy, K, (ext, estride), cameras, cnt[:, 0], r["ws"], r["pose"], r["result"],
-                                                       b["pose"], b["result"], b["mask"], iterations=iterations, seed=seed, coord_major=True)
-            if pose_cov is not None:
-                c = self._cov_bufs(r, S, dev)
-                _pose.pose_covariance_rig_into(cpts, fxy, K, (ext, estride), cameras, cnt[:, 0], r["pose"], r["result"], b["mask"], c["cov"],
-                                               c["info"], c["stat"], sigma_px=pose_cov[0], coord_major=True)
-                rig.update(cov=c["cov"], info=c["info"], cov_stat=c["stat"])
-                c = self._cov_bufs(b, B, dev)   # per image: the frame form at E_c o rig pose on the image's own rows
-                _pose.pose_covariance_batch_into(cpts, fxy, K, cnt[:, 0], b["pose"], b["result"], b["mask"], c["cov"], c["info"], c["stat"],
-                                                 sigma_px=pose_cov[0], coord_major=True)
-                per.update(cov=c["cov"], info=c["info"], cov_stat=c["stat"])
-            return per, K, rig
-        res, R, t, mask = _pose.solve_pnp_ransac_batch_into(cpts, fxy, K, cnt[:, 0], b["ws"], b["pose"], b["result"], b["mask"],
-                                                            iterations=iterations, seed=seed, coord_major=True)
-        pose = {"result": res, "R": R, "t": t, "inliers": mask}
-        if pose_cov is not None:
-            c = self._cov_bufs(b, B, dev)
-            _pose.pose_covariance_batch_into(cpts, fxy, K, cnt[:, 0], b["pose"], b["result"], b["mask"], c["cov"], c["info"], c["stat"],
-                                             sigma_px=pose_cov[0], coord_major=True)
-            pose.update(cov=c["cov"], info=c["info"], cov_stat=c["stat"])
-        return pose, K, None
-
-    def _forward_async(self, slot, pc_data_dict, img, mode, inputs_stable, pose_K=None, pose_iterations=10000, pose_seed=0, eval_into=None,
-                       cameras=1, rig_ext=None, fuse_into=None, pose_cov=None):
-        P = self._pack(img.device)
-        if inputs_stable:
-            for k in ("points", "neighbors", "subsampling", "upsampling"):
-                for t in pc_data_dict[k]:
-                    if not t.is_contiguous() or (k != "points" and t.dtype != torch.int32):
-                        raise _lib.CofiError("inputs_stable=True reads the inputs in place: contiguous tensors and int32 tables only (%s)" % k)
-            if not (pc_data_dict["feats"].is_contiguous() and img.is_contiguous()):
-                raise _lib.CofiError("inputs_stable=True reads the inputs in place: contiguous feats / img only")
-        points = [p.contiguous() for p in pc_data_dict["points"]]
-        tabs = [[self._as_idx32(t) for t in pc_data_dict[k]] for k in ("neighbors", "subsampling", "upsampling")]
-        # submissions in flight fill the GPU by themselves: the per-submission graph is a linear chain (intra-frame
-        # fork/join only adds join latency then — measured 254 vs 331 frames/s at two frames in flight; DESIGN.md §3)
-        outs = self._graph_forward(P, points, tabs[0], tabs[1], tabs[2], pc_data_dict["feats"].contiguous(), img.contiguous(), mode, None,
-                                   None, slot=slot, branch_mask=self.async_branch_mask,
-                                   order=pc_data_dict.get("order"), inputs_stable=inputs_stable, cameras=cameras,
-                                   sorted_tables=bool(pc_data_dict.get("sorted_tables")))
-        hosts = self.__dict__.setdefault("_count_host", {})   # one pinned landing buffer per slot (a slot is finished before it is reused)
-        host = hosts.get((slot, len(outs)))
-        if host is None:
-            host = hosts[(slot, len(outs))] = torch.empty((len(outs), 2), dtype=torch.int32, pin_memory=True)
-        host.copy_(outs[0]["count_all"], non_blocking=True)
-        pose, K_dev, rig_pose = (None, None, None) if pose_K is None else self._enqueue_pose(slot, outs, pose_K, pose_iterations, pose_seed,
-                                                                                             cameras, rig_ext, pose_cov)
-        if eval_into is not None:   # the evaluation monitors of the submission: one launch behind the pose tail
-            from . import evaluation
-
-            evaluation.eval_monitors({"out": outs, "pose": pose}, K_dev, eval_into[1], eval_into[0], eval_into[2])
-        if fuse_into is not None:   # the registered cloud of the submission: four launches behind the pose tail
-            from . import fusion
-
-            im = img.contiguous().reshape((-1,) + tuple(img.shape[-3:]))
-            fusion.fuse_into(points[0], im, pose, K_dev, fuse_into, result=pose["result"], cameras=cameras,
-                             k_scale=float(im.shape[3]) / float(4 * (im.shape[3] // 8)))
-        done = torch.cuda.Event()
-        done.record()
-        handle = {"out": outs, "count_host": host, "done": done}
-        if fuse_into is not None:
-            handle["fusion"] = fuse_into
-        if pose is not None:
-            handle["pose"] = pose
-        if rig_pose is not None:
-            handle["rig_pose"] = rig_pose
-        return handle
+        return S
 
     @torch.no_grad()
     def forward_val_async(self, slot: int, pc_data_dict, img, fine_center_kpt_coors, fine_pc_inline_index, inputs_stable: bool = False,
@@ -774,21 +740,10 @@ class CoFiI2P(nn.Module):
             if inputs_stable:
                 raise _lib.CofiError("inputs_stable=True reads the labels in place: one integer dtype for both")
             labels = [t.to(torch.int64) for t in labels]
-        if inputs_stable:   # as forward_async: the graph reads these very tensors
-            for k in ("points", "neighbors", "subsampling", "upsampling"):
-                for t in pc_data_dict[k]:
-                    if not t.is_contiguous() or (k != "points" and t.dtype != torch.int32):
-                        raise _lib.CofiError("inputs_stable=True reads the inputs in place: contiguous tensors and int32 tables only (%s)" % k)
-            if not (pc_data_dict["feats"].is_contiguous() and img.is_contiguous()):
-                raise _lib.CofiError("inputs_stable=True reads the inputs in place: contiguous feats / img only")
+        inputs = ForwardInputs.prepare(pc_data_dict, img, labels, inputs_stable)   # as forward_async: stable inputs are read in place
         with ops.arithmetic(self.arithmetic):
-            P = self._pack(img.device)
-            points = [p.contiguous() for p in pc_data_dict["points"]]
-            tabs = [[self._as_idx32(t) for t in pc_data_dict[k]] for k in ("neighbors", "subsampling", "upsampling")]
-            outs = self._graph_forward(P, points, tabs[0], tabs[1], tabs[2], pc_data_dict["feats"].contiguous(), img.contiguous(), "val",
-                                       labels[0], labels[1], slot=slot, branch_mask=self.async_branch_mask,
-                                       order=pc_data_dict.get("order"), inputs_stable=inputs_stable,
-                                       sorted_tables=bool(pc_data_dict.get("sorted_tables")))
+            outs = self._graph_forward(self._pack(img.device), inputs, "val", slot=slot, branch_mask=self.async_branch_mask,
+                                       inputs_stable=inputs_stable)
         done = torch.cuda.Event()
         done.record()
         return {"out": outs, "done": done, "mode": "val"}
@@ -870,22 +825,16 @@ class CoFiI2P(nn.Module):
         if not img.is_cuda:
             raise _lib.CofiError("CoFiI2P.forward needs CUDA (HIP) tensors: there is no CPU path")
         _lib.load()
-        dev = img.device
-        P = self._pack(dev)
-        points = [p.contiguous() for p in pc_data_dict["points"]]
-        neighbors = [self._as_idx32(t) for t in pc_data_dict["neighbors"]]
-        subsampling = [self._as_idx32(t) for t in pc_data_dict["subsampling"]]
-        upsampling = [self._as_idx32(t) for t in pc_data_dict["upsampling"]]
-        feats = pc_data_dict["feats"].contiguous()
-        order = pc_data_dict.get("order")  # optional: spatially sorted processing order per stage (preprocess.morton_order)
-        srt = bool(pc_data_dict.get("sorted_tables"))  # optional: the promise of sorted neighbour rows (preprocess.build_pyramid)
+        P = self._pack(img.device)
+        # optional keys of the pyramid: "order", the spatially sorted processing order per stage (preprocess.morton_order), and
+        # "sorted_tables", the promise of sorted neighbour rows (preprocess.build_pyramid)
+        i = ForwardInputs.prepare(pc_data_dict, img, (fine_center_kpt_coors, fine_pc_inline_index))
         auto = self._auto_graphs and not self._use_graphs and taps is None
         if (self._use_graphs or auto) and taps is None:
-            o = self._graph_forward(P, points, neighbors, subsampling, upsampling, feats, img.contiguous(), mode, fine_center_kpt_coors,
-                                    fine_pc_inline_index, order=order, sorted_tables=srt)[0]
+            o = self._graph_forward(P, i, mode)[0]
         else:
-            o = self._run_device(P, points, neighbors, subsampling, upsampling, feats, img, mode, fine_center_kpt_coors,
-                                 fine_pc_inline_index, taps=taps, order=order, sorted_tables=srt)[0]
+            o = self._run_device(P, i.points, i.neighbors, i.subsampling, i.upsampling, i.feats, i.img, mode, i.kpt, i.inl, taps=taps,
+                                 order=i.order or None, sorted_tables=i.sorted_tables)[0]
         own = (lambda t: t.clone() if torch.is_tensor(t) else t) if auto else (lambda t: t)   # unasked graphs: results the caller owns
         if mode in ("train", "val"):
             return tuple(own(t) for t in (o["img_desc"], o["pc_desc"], o["img_score"], o["pc_score"], o["patches"], o["fine_pc"])) + (None, None)

@@ -4,6 +4,7 @@ Every function takes torch CUDA tensors, validates layout, and enqueues the HIP 
 libcofi_hip.so on the CURRENT torch stream.  Row-major 2-D tensors may be column slices of a wider
 buffer: the leading dimension is `stride(0)`, `stride(1)` must be 1.
 """
+import contextlib
 import ctypes
 import math
 from typing import Optional
@@ -30,6 +31,12 @@ GEMM_MODE = os.environ.get("COFI_GEMM", "bf16x3")
 # Which intra-frame fork/join branches are taken (see Branch).  With >= 2 frames in flight the frames themselves fill
 # the GPU and intra-frame forks only add join overhead; with one frame in flight they shorten the critical path.
 BRANCH_MASK = 7
+
+# The switches of this module that decide which kernels a forward enqueues: attributes, or zero-argument functions (arithmetic of the
+# calling thread, per-call environment reads).  network.routing_state() collects them, and those of kpfpn / transformer / network, into
+# the key of every recording; a new switch is declared here (tests/test_host_cpu.py checks every COFI_* environment read against this).
+ROUTING = ("gemm_mode", "f16x3_big", "F16X3_WPRE", "X6_W_SPLIT", "FINALIZE_MIN_FRAMES", "kpconv_records", "kpconv_prefix", "maxpool_slice",
+           "MAXPOOL_SLICE_MIN_FRAMES", "MAXPOOL_SLICE_MAX_ROWS", "ATTN_MODE", "ATTN_PRESPLIT_ROWS", "TAIL_FRAG")
 
 
 _TLS = threading.local()
@@ -326,6 +333,22 @@ _WS_STATS = Workspace()
 def set_workspace_slot(slot: int):
     """Select the scratch namespace used by subsequently enqueued / captured kernels (one per frame in flight)."""
     Workspace.slot = int(slot)
+
+
+@contextlib.contextmanager
+def recording_scope(slot: int, branch_mask: int):
+    """Warm-up, capture and replay of one slot's recording: its scratch namespace and the intra-frame forks the capture records
+    (BRANCH_MASK).  Both are restored on the way out, so an exception during warm-up / capture does not leave later eager forwards in
+    this slot's scratch namespace."""
+    global BRANCH_MASK
+    saved_mask, saved_slot = BRANCH_MASK, Workspace.slot
+    set_workspace_slot(slot)
+    BRANCH_MASK = branch_mask
+    try:
+        yield
+    finally:
+        set_workspace_slot(saved_slot)
+        BRANCH_MASK = saved_mask
 
 
 # Statistics partials -> per-channel scale / shift: finalized once per (statistics, affine pair) by cofi_norm_finalize and read by every

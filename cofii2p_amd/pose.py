@@ -440,6 +440,74 @@ def pose_covariance_rig(object_points: torch.Tensor, image_points: torch.Tensor,
                                     stat, sigma_px, coord_major)
 
 
+class PoseTail:
+    """The pose tail of one forward_async slot: the buffers the slot owns - per (B, cap, iterations): ws, pose, result, mask, K; the rig
+    set and the covariance sets, each made when a submission first asks for it - and the launches that fill them."""
+
+    def __init__(self):
+        self.sets = {}
+
+    def enqueue(self, outs, K, iterations, seed, cameras=1, rig_ext=None, pose_cov=None):
+        """the batched pose tail of a submission (with rig_ext = (ext, rig stride): the rig solve; with pose_cov = (sigma_px or None,): the
+        covariance launch behind it), on the current stream -> (handle["pose"], K on the device, handle["rig_pose"] or None)"""
+        if "coarse_pts_all" not in outs[0]:
+            raise _lib.CofiError("forward_async(pose_K=...): the batched pose tail reads the outputs of match_finish, which serves fine "
+                                 "feature maps of at most 128 channels; this model's fine map is wider")
+        cpts, fxy, count = outs[0]["coarse_pts_all"], outs[0]["fine_xy_all"], outs[0]["count_all"][:, 0]
+        B, cap, dev = cpts.shape[0], cpts.shape[1], cpts.device
+        if not torch.is_tensor(K):
+            K = torch.as_tensor(np.asarray(K, dtype=np.float32))
+        if tuple(K.shape) not in ((B, 3, 3), (3, 3)):
+            raise _lib.CofiError("forward_async: pose_K must be (B,3,3) = %s or (3,3), got %s" % ((B, 3, 3), tuple(K.shape)))
+        key = (B, cap, int(iterations))
+        b = self.sets.get(key)
+        if b is None:
+            b = self.sets[key] = {"ws": torch.empty(pnp_batch_workspace(iterations, B), dtype=torch.uint8, device=dev),
+                                  "pose": torch.empty((B, 12), dtype=torch.float32, device=dev),
+                                  "result": torch.empty((B, 3), dtype=torch.int32, device=dev),
+                                  "mask": torch.empty((B, cap), dtype=torch.uint8, device=dev),
+                                  "K": torch.empty((B, 3, 3), dtype=torch.float32, device=dev)}
+        if not (K.is_cuda and K.device == dev and K.dtype == torch.float32 and K.dim() == 3 and K.is_contiguous()):
+            b["K"].copy_(K, non_blocking=True)   # broadcasts a (3,3); a device K of another dtype is converted on the device
+            K = b["K"]
+
+        def covariance(holder, frames, launch, *operands):
+            """one covariance launch into the float64 set `holder` owns for `frames` bodies -> the three handle entries"""
+            c = holder.get("cov")
+            if c is None:
+                c = holder["cov"] = [torch.empty((frames,) + s, dtype=torch.float64, device=dev) for s in ((6, 6), (6, 6), (4,))]
+            launch(cpts, fxy, K, *operands, b["mask"], *c, sigma_px=pose_cov[0], coord_major=True)
+            return dict(zip(("cov", "info", "cov_stat"), c))
+
+        if rig_ext is None:
+            res, R, t, mask = solve_pnp_ransac_batch_into(cpts, fxy, K, count, b["ws"], b["pose"], b["result"], b["mask"],
+                                                          iterations=iterations, seed=seed, coord_major=True)
+            pose = {"result": res, "R": R, "t": t, "inliers": mask}
+            if pose_cov is not None:
+                pose.update(covariance(b, B, pose_covariance_batch_into, count, b["pose"], b["result"]))
+            return pose, K, None
+        S = B // cameras
+        ext, estride = rig_ext
+        r = b.get("rig")
+        if r is None:
+            r = b["rig"] = {"ws": torch.empty(pnp_rig_workspace(iterations, S), dtype=torch.uint8, device=dev),
+                            "pose": torch.empty((S, 12), dtype=torch.float32, device=dev),
+                            "result": torch.empty((S, 3), dtype=torch.int32, device=dev)}
+        if not (ext.is_cuda and ext.device == dev):   # a host set: into a buffer of the slot, as K
+            buf = r.get("ext")
+            if buf is None or buf.shape != ext.shape:
+                buf = r["ext"] = torch.empty(tuple(ext.shape), dtype=torch.float32, device=dev)
+            buf.copy_(ext, non_blocking=True)
+            ext = buf
+        rig, per = solve_pnp_ransac_rig_into(cpts, fxy, K, (ext, estride), cameras, count, r["ws"], r["pose"], r["result"],
+                                             b["pose"], b["result"], b["mask"], iterations=iterations, seed=seed, coord_major=True)
+        if pose_cov is not None:
+            rig.update(covariance(r, S, pose_covariance_rig_into, (ext, estride), cameras, count, r["pose"], r["result"]))
+            # per image: the frame form at E_c o rig pose on the image's own rows
+            per.update(covariance(b, B, pose_covariance_batch_into, count, b["pose"], b["result"]))
+        return per, K, rig
+
+
 def pose_nees(pose, P_gt, info: torch.Tensor, stat: torch.Tensor) -> torch.Tensor:
     """Normalised estimation error squared of B poses against ground truth (cofi_pose_nees): e = (log(R_gt R_est^T), t_gt - exp(omega)
     t_est), nees = e^T info e - chi-square with 6 degrees of freedom for a calibrated covariance; NaN where stat[:, 0] == 0.  pose (B,12)

@@ -15,6 +15,7 @@ from typing import Dict, List, Optional, Tuple
 import torch
 
 from . import loss as L
+from .network import routing_state
 
 
 def step_losses(model, pc_data_dict: Dict, img: torch.Tensor, batch: Dict[str, torch.Tensor], opt, mode: str = "train") -> Tuple:
@@ -147,7 +148,7 @@ class GraphedTrainStep:
             sig += [tuple(t.shape) for t in pc[k]]
         sig.append(tuple(pc["feats"].shape))
         sig += [(k, tuple(batch[k].shape), str(batch[k].dtype)) for k in sorted(batch)]
-        return tuple(sig)
+        return tuple(sig) + routing_state()   # a switch flipped since the recording: another launch sequence, a new recording
 
     def _allocate(self, pc, img, batch, dev):
         spc = {"points": [torch.empty(t.shape, dtype=torch.float32, device=dev) for t in pc["points"]],

@@ -131,6 +131,7 @@ class TokenStreams:
 
 
 FUSED_CHAIN = os.environ.get("COFI_TRANSFORMER_CHAIN", "1") != "0"
+ROUTING = ("JOINT_SELF", "TAIL_MAX_ROWS", "FUSED_CHAIN")   # this module's part of the key of every recording (ops.ROUTING)
 
 
 def _chain_ok(ts: "TokenStreams", kinds, frames: int) -> bool:

@@ -1,6 +1,7 @@
 """End-to-end parity of CoFiI2P.forward on the GPU against (i) the reference's recorded outputs
 (tests/golden/frame_*.npz) and (ii) the CPU oracle's intermediate taps.  Tolerance: 1e-3 absolute on
 L2-normalised descriptors / sigmoid scores (BASELINE.json north_star), exact on integer outputs."""
+import contextlib
 import os
 
 import numpy as np
@@ -247,6 +248,52 @@ def test_hipgraph_replay_equals_eager(model):
     assert len(model._graphs) == 1  # one capture served both frames
     assert not torch.equal(outs[11][1], outs[12][1])
     model.enable_graphs(False)
+
+
+@pytest.mark.parametrize("switch", ["DECODER_CONCAT", "COFI_KPCONV_RECORDS"])
+def test_flipped_switch_records_anew(model, switch):
+    """A switch flipped inside the process (network.routing_state is part of every recording's key) is a new recording with the bits
+    of the eager launches under that switch; flipped back, the first recording replays again.  DECODER_CONCAT changes the last bits (a
+    stale replay shows in the values), COFI_KPCONV_RECORDS=0 gives the same bits (it shows only in the count)."""
+    from cofii2p_amd import kpfpn
+    from cofii2p_amd.preprocess import build_pyramid
+    from cofii2p_amd.synth import make_frame, subsample_indices
+
+    @contextlib.contextmanager
+    def flipped():
+        with pytest.MonkeyPatch.context() as mp:
+            if switch == "DECODER_CONCAT":
+                mp.setattr(kpfpn, "DECODER_CONCAT", True)
+            else:
+                mp.setenv("COFI_KPCONV_RECORDS", "0")
+            yield
+
+    fr = make_frame(11, 4096)
+    sub = [torch.from_numpy(s).to(DEV) for s in subsample_indices(4096, 5, seed=11)]
+    pyr = build_pyramid(torch.from_numpy(fr.points).to(DEV), sub)
+    pyr["feats"] = torch.from_numpy(fr.feats).to(DEV)
+    img = torch.from_numpy(fr.img)[None].to(DEV)
+    run = lambda: [t.clone() for t in model(pyr, img, None, None, None, "test")[:6]]
+    model.enable_graphs(False)   # (drops every recording: the eager references come first)
+    with flipped():
+        eager = run()
+    try:
+        model.enable_graphs(True)
+        first = run()
+        n0 = len(model._graphs)
+        with flipped():
+            second = run()
+            assert len(model._graphs) == n0 + 1
+        for a, b in zip(second, eager):
+            assert torch.equal(a, b)
+        if switch == "DECODER_CONCAT":
+            assert not all(torch.equal(a, b) for a, b in zip(second, first))
+        third = run()
+        assert len(model._graphs) == n0 + 1
+        for a, b in zip(third, first):
+            assert torch.equal(a, b)
+    finally:
+        model.enable_graphs(False)
 
 
 def test_forward_async_reads_stable_inputs_in_place(model):

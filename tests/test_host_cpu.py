@@ -452,3 +452,130 @@ def test_fragment_order_is_the_mfma_b_operand_order():
     f = ops.fragment_order(w).reshape(2, -1)
     for (p, T, s, lane, i) in [(0, 0, 0, 0, 0), (1, 1, 2, 37, 5), (0, 1, 1, 63, 7), (1, 0, 2, 31, 3)]:
         assert int(f[p, ((T * (K // 16) + s) * 64 + lane) * 8 + i]) == int(w[p, 32 * T + (lane & 31), 16 * s + 8 * (lane >> 5) + i])
+
+
+# COFI_* environment reads that are no entry of a ROUTING tuple, each with the reason
+ROUTING_EXEMPT = {
+    "COFI_GEMM": "ops.GEMM_MODE: read through ops.gemm_mode, which is listed",
+    "COFI_F16X3": "ops.F16X3_BIG: read through ops.f16x3_big, which is listed",
+    "COFI_HIPCC_FLAGS": "compiler flags of the library build: no launch decision of a forward",
+    "COFI_DEAD_MAPS": "the instance attribute compute_unused_image_maps, itself part of the recording key",
+    "COFI_ASYNC_BRANCH_MASK": "the instance attribute async_branch_mask: the branch mask of the recording key",
+}
+
+
+def _cofi_env_reads(tree):
+    """(variable, top-level statement) of every os.environ.get("COFI_...") of a module"""
+    import ast
+
+    for stmt in tree.body:
+        for node in ast.walk(stmt):
+            if (isinstance(node, ast.Call) and isinstance(node.func, ast.Attribute) and node.func.attr == "get"
+                    and isinstance(node.func.value, ast.Attribute) and node.func.value.attr == "environ"
+                    and isinstance(node.func.value.value, ast.Name) and node.func.value.value.id == "os" and node.args
+                    and isinstance(node.args[0], ast.Constant) and str(node.args[0].value).startswith("COFI_")):
+                yield node.args[0].value, stmt
+
+
+def test_every_switch_is_part_of_the_routing_state(monkeypatch):
+    """Every COFI_* environment read of the package is the value of a module attribute named in its module's ROUTING tuple, sits inside
+    a function named there, or is exempt above with a reason: a new switch cannot appear without deciding whether recordings depend on
+    it.  network.routing_state() - part of the key of every recording - is hashable and follows an attribute-style switch, a dict-valued
+    one and a per-call environment read; GraphedTrainStep's signature follows it too."""
+    import ast
+    import glob
+    import importlib
+
+    import cofii2p_amd
+    from cofii2p_amd import kpfpn, network, ops
+    from cofii2p_amd.train_step import GraphedTrainStep
+
+    seen, exempt_used = 0, set()
+    for path in sorted(glob.glob(os.path.join(os.path.dirname(cofii2p_amd.__file__), "*.py"))):
+        reads = list(_cofi_env_reads(ast.parse(open(path).read())))
+        if not reads:
+            continue
+        stem = os.path.splitext(os.path.basename(path))[0]
+        routing = getattr(importlib.import_module("cofii2p_amd." + stem), "ROUTING", ())
+        for var, stmt in reads:
+            seen += 1
+            if isinstance(stmt, ast.Assign):
+                owners = [t.id for t in stmt.targets if isinstance(t, ast.Name)]
+            else:
+                owners = [stmt.name] if isinstance(stmt, ast.FunctionDef) else []
+            if any(o in routing for o in owners):
+                assert var not in ROUTING_EXEMPT, var
+            else:
+                assert var in ROUTING_EXEMPT, "%s (%s.py, line %d) is neither in ROUTING nor exempt" % (var, stem, stmt.lineno)
+                exempt_used.add(var)
+    assert seen >= 19 and exempt_used == set(ROUTING_EXEMPT)
+    for module in (ops, kpfpn, network, importlib.import_module("cofii2p_amd.transformer")):
+        assert module.ROUTING and all(hasattr(module, name) for name in module.ROUTING), module.__name__
+
+    pc = {k: [torch.zeros(8, 3, dtype=torch.float32 if k == "points" else torch.int32)] for k in ("points", "neighbors", "subsampling", "upsampling")}
+    pc["feats"] = torch.zeros(8, 4)
+    sig = lambda: GraphedTrainStep._signature(pc, torch.zeros(1, 3, 16, 16), {"pc_kpt_idx": torch.zeros(4, dtype=torch.int64)})
+    states, sigs = [network.routing_state()], [sig()]
+    assert isinstance(states[0], tuple) and hash(states[0]) == hash(network.routing_state()) and sigs[0] == sig()
+    assert ops.gemm_mode() in states[0] and ops.f16x3_big() in states[0]
+    monkeypatch.setattr(kpfpn, "DECODER_CONCAT", not kpfpn.DECODER_CONCAT)
+    states.append(network.routing_state()), sigs.append(sig())
+    monkeypatch.setitem(kpfpn.DECODER_PROJECT_MIN_ROWS, "decoder4", 4096)
+    states.append(network.routing_state()), sigs.append(sig())
+    monkeypatch.setenv("COFI_KPCONV_RECORDS", "0" if ops.kpconv_records() else "1")
+    states.append(network.routing_state()), sigs.append(sig())
+    with ops.arithmetic("f32" if ops.gemm_mode() != "f32" else "bf16x6"):
+        states.append(network.routing_state())
+    assert len(set(states)) == 5 and len(set(sigs)) == 4
+    n = len(states[0])
+    assert all(len(s) == n for s in states) and all(s[:-n] == sigs[0][:-n] and s[-n:] == st for s, st in zip(sigs, states))   # shapes, then the state
+
+
+def test_forward_inputs_record():
+    """network.ForwardInputs: prepared once (contiguous tensors, int32 tables), flattened and rebuilt over another list of tensors in
+    the same structure, with and without `order` and labels; inputs_stable=True refuses whatever would need a copy or a conversion."""
+    from cofii2p_amd._lib import CofiError
+    from cofii2p_amd.network import ForwardInputs
+
+    def pyramid(order):
+        pc = {"points": [torch.rand(32, 3), torch.rand(16, 3)], "feats": torch.rand(32, 4)}
+        for i, k in enumerate(("neighbors", "subsampling", "upsampling")):
+            pc[k] = [torch.full((32 >> (i == 1), 4), i, dtype=torch.int32), torch.full((16, 4), i, dtype=torch.int32)][:1 if i else 2]
+        if order:
+            pc["order"] = [torch.arange(32, dtype=torch.int32), torch.arange(16, dtype=torch.int32)]
+            pc["sorted_tables"] = True
+        return pc
+
+    img = torch.rand(1, 3, 16, 32)
+    labels = (torch.ones(2, 5, dtype=torch.int64), torch.arange(5))
+    for order in (False, True):
+        for lab in ((None, None), labels):
+            pc = pyramid(order)
+            rec = ForwardInputs.prepare(pc, img, lab, inputs_stable=True)
+            assert rec.order == (pc["order"] if order else []) and rec.sorted_tables is order and rec.kpt is lab[0] and rec.inl is lab[1]
+            assert all(a is b for a, b in zip(rec.points + rec.neighbors + rec.subsampling + rec.upsampling, pc["points"] + pc["neighbors"] + pc["subsampling"] + pc["upsampling"]))
+            flat = rec.flat()
+            assert len(flat) == 6 + 2 * order + 4 and flat[-4] is pc["feats"] and flat[-3] is img and flat[-2] is lab[0] and flat[-1] is lab[1]
+            other = [None if t is None else t.clone() for t in flat]
+            twin = rec.rebuild(other)
+            assert [len(f) for f in twin[:5]] == [len(f) for f in rec[:5]] == [2, 2, 1, 1, 2 * order] and twin.sorted_tables is order
+            assert all(a is b for a, b in zip(twin.flat(), other)) and rec.rebuild(flat) == rec
+    # without the promise anything goes: tensors are made contiguous
+    pc = pyramid(False)
+    pc["feats"] = torch.zeros(32, 8)[:, :4]
+    pc["points"][1] = torch.rand(3, 16).T
+    rec = ForwardInputs.prepare(pc, img.expand(2, 3, 16, 32))
+    assert all(t.is_contiguous() for t in rec.flat() if t is not None) and torch.equal(rec.points[1], pc["points"][1])
+    # with it: a strided feats, a non-contiguous table and an int64 table are refused
+    bad = pyramid(True)
+    bad["feats"] = torch.zeros(32, 8)[:, :4]
+    with pytest.raises(CofiError, match="contiguous feats / img only"):
+        ForwardInputs.prepare(bad, img, inputs_stable=True)
+    bad = pyramid(True)
+    bad["neighbors"][1] = torch.zeros(4, 16, dtype=torch.int32).T
+    with pytest.raises(CofiError, match=r"contiguous tensors and int32 tables only \(neighbors\)"):
+        ForwardInputs.prepare(bad, img, inputs_stable=True)
+    bad = pyramid(False)
+    bad["upsampling"] = [t.long() for t in bad["upsampling"]]
+    with pytest.raises(CofiError, match=r"contiguous tensors and int32 tables only \(upsampling\)"):
+        ForwardInputs.prepare(bad, img, labels, inputs_stable=True)
