@@ -67,6 +67,9 @@ static inline AttnLayout attn_layout(int L, int S, int H, int frames) {
     return a;
 }
 
+// 2^x as the hardware gives it (v_exp_f32): every weight 2^(m_s - m), in the producer's softmax and in every merge, goes through here
+__device__ __forceinline__ float attn_exp2(float x) { return __builtin_amdgcn_exp2f(x); }
+
 // merged, normalised output of query row l (frame f, head h), 16-byte chunk `ch` (d = 4 ch .. 4 ch + 3).  Every load is
 // issued before the first use: one round trip whatever KS is.
 __device__ __forceinline__ float4 attn_merged_chunk(const float *parts, const AttnLayout &lay, int f, int H, int h, int l, int ch) {
@@ -93,7 +96,7 @@ __device__ __forceinline__ float4 attn_merged_chunk(const float *parts, const At
 #pragma unroll
     for (int s = 0; s < COFI_ATTN_MAX_KS; ++s)
         if (s < lay.KS) {
-            const float sc = __builtin_amdgcn_exp2f(m[s] - mm);
+            const float sc = attn_exp2(m[s] - mm);
             lsum += ls[s] * sc;
             r.x += o[s].x * sc; r.y += o[s].y * sc; r.z += o[s].z * sc; r.w += o[s].w * sc;
         }

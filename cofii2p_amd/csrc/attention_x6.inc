@@ -2,8 +2,10 @@
 // scaled Q and the softmax weights P - is cut into three bf16 planes (hi / mid / lo, x == hi + mid + lo exactly) and each contraction
 // is the six products lo.hi + hi.lo + mid.mid + mid.hi + hi.mid + hi.hi on v_mfma_f32_32x32x16_bf16 (fp32 accumulation; the dropped
 // terms are below 2^-24 of the product).  A 32 x 32 x 32 unit costs 2 x 6 MFMAs of 32 clocks instead of 16 of 64: the matrix pipe
-// roof goes from 157 TF/s (fp32 instruction) to 2500 / 6 = 417 TF/s.  Included by attention.hip inside its anonymous namespace: same
-// work partition (attn_layout), same slot output, same merge - only the unit's arithmetic and the LDS image differ.
+// roof goes from 157 TF/s (fp32 instruction) to 2500 / 6 = 417 TF/s.  Included by attention.hip inside its anonymous namespace, below
+// the skeleton it shares with the fp32 kernel (work decode, Q-scale fold, mask_tail, softmax_step, store_slot - see that file's
+// header): same work partition (attn_layout), same slot output, same merge - this file holds the unit's arithmetic, the LDS image
+// and staging that go with it, and the main-loop schedule.
 //
 // LDS image of a step: KPH K tiles + KPH V tiles, each as three bf16 planes of 32 rows x 64 B (+ 16 B pad: the 16-byte fragment reads
 // of 8 consecutive rows fall into 8 different bank groups):
@@ -85,13 +87,8 @@ __global__ __launch_bounds__(64 * NW, 2) void attention_x6_kernel(AttnArgs a) {
     const int li = lane & 31, lh = lane >> 5;
     const int ph = wave >> 1, qb_w = wave & 1;
     const AttnLayout &lay = a.lay;
-    const int lb = xcd_contiguous_block(blockIdx.x, gridDim.x);
-    const int sp = lb / lay.KS, ks = lb - sp * lay.KS;
-    const int fh = sp / lay.QSB, qsb = sp - fh * lay.QSB;
-    const int f = fh / a.H, h = fh - f * a.H;
-    const int base = lay.P / lay.KS, rem = lay.P - base * lay.KS;
-    const int kb0 = ks * base + min(ks, rem), nblk = base + (ks < rem ? 1 : 0);
-    const int nsteps = (nblk + KPH - 1) / KPH;
+    const AttnUnit u = attn_unit(blockIdx.x, gridDim.x, a);
+    const int f = u.f, h = u.h, kb0 = u.kb0, nblk = u.nblk, nsteps = u.nsteps;
     const float *Kf = a.K + (size_t)f * a.S * a.ldk + h * D, *Vf = a.V + (size_t)f * a.S * a.ldv + h * D;
 
     // ---- staging.  K: thread (tile, key row, 8-channel piece); V: thread (channel, tile, k-step, half).  Buffer loads: rows past S
@@ -167,37 +164,16 @@ __global__ __launch_bounds__(64 * NW, 2) void attention_x6_kernel(AttnArgs a) {
     // ---- prologue
     stage_load(0);
     f32x4 qraw[4];   // lane (q = li, h): Q[q][16 s + 8 h + 4 j + e] in qraw[2 s + j][e]
-    const int qblk = qsb * QG + qb_w;            // this wave's query block; past the last one: idle wave (clamped loads, no slot)
+    const int qblk = u.qsb * QG + qb_w;          // this wave's query block; past the last one: idle wave (clamped loads, no slot)
     {
         const int q = min(qblk * 32 + li, a.L - 1);
         const float *qp = a.Q + ((size_t)f * a.L + q) * a.ldq + h * D + 8 * lh;
 #pragma unroll
         for (int c = 0; c < 4; ++c) qraw[c] = *reinterpret_cast<const f32x4 *>(qp + 16 * (c >> 1) + 4 * (c & 1));
     }
-    {   // token-axis norm of this head's 32 Q columns from the projection's column partials (as attention_flat_kernel)
-        const int col = tid & 31, php = tid >> 5;
-        if (a.q_colpart) {
-            const float *cp = a.q_colpart + ((size_t)f * a.q_nslab * a.q_ncols + h * D + col) * 2 + 1;
-            float acc = 0.f;
-            for (int b = php; b < a.q_nslab; b += 2 * NW) acc += cp[(size_t)b * a.q_ncols * 2];
-            s_part[php * 32 + col] = acc;
-        }
-        stage_store();
-        __syncthreads();
-        if (tid < 32) {
-            float v = 1.0f;
-            if (a.q_colpart) {
-                float t = 0.f;
-#pragma unroll
-                for (int p = 0; p < 2 * NW; ++p) t += s_part[p * 32 + tid];
-                v = 1.0f / fmaxf(sqrtf(t), a.q_eps);
-            } else if (a.qs) {
-                v = a.qs[((size_t)f * a.H + h) * D + tid];
-            }
-            s_qs[tid] = v;
-        }
-        __syncthreads();
-    }
+    q_scale_partials(a, u, s_part);
+    stage_store();
+    q_scale_fold(a, u, s_part, s_qs);
     CofiFrag qp3[3][2];   // planes of q * colscale * softmax scale * log2(e): the B operand of S^T = K . Q^T ([2]: re-read from LDS per unit)
     const unsigned char *my_qlo = s_qlo + (qb_w * 2 * 64 + lane) * 16;
 #pragma unroll
@@ -238,30 +214,6 @@ __global__ __launch_bounds__(64 * NW, 2) void attention_x6_kernel(AttnArgs a) {
         for (int p = 0; p < 3; ++p)
 #pragma unroll
             for (int st = 0; st < 2; ++st) fr[p][st].u = *reinterpret_cast<const uint4 *>(tile + p * PT + li * ROWB + 32 * st + 16 * lh);
-    };
-    auto mask_tail = [&](int kb, f32x16 &s) __attribute__((always_inline)) {
-        const int k0 = kb * 32;
-#pragma unroll
-        for (int r = 0; r < 16; ++r)
-            if (k0 + (r & 3) + 8 * (r >> 2) + 4 * lh >= a.S) s[r] = -INFINITY;
-    };
-    auto softmax = [&](f32x16 &s) __attribute__((always_inline)) {  // online softmax (base 2); returns P in s, rescales o
-        float bmax = -1e30f;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) bmax = fmaxf(bmax, s[r]);
-        bmax = fmaxf(bmax, __shfl_xor(bmax, 32, 64));
-        const float m_new = fmaxf(m_run, bmax);
-        const float alpha = fast_exp2(m_run - m_new);
-        float psum = 0.f;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            s[r] = fast_exp2(s[r] - m_new);
-            psum += s[r];
-        }
-        l_run = l_run * alpha + psum;
-        m_run = m_new;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) o[r] *= alpha;
     };
     auto split_p = [&](const f32x16 &p, CofiFrag(&pp)[3][2]) __attribute__((always_inline)) {   // P -> the B operand planes, in place
 #pragma unroll
@@ -317,7 +269,7 @@ __global__ __launch_bounds__(64 * NW, 2) void attention_x6_kernel(AttnArgs a) {
         front();
         if constexpr (!(DBG & 2)) barrier_lds();       // every wave holds its fragments of tile t in registers
         if constexpr (!(DBG & 8)) stage_store();       // the staging registers die before the softmax
-        if constexpr (!(DBG & 4)) softmax(sC);         // (the partial last key block of a pair is never in these steps)
+        if constexpr (!(DBG & 4)) softmax_step(sC, o, m_run, l_run);         // (the partial last key block of a pair is never in these steps)
         if constexpr (!(DBG & 16)) pv(sC, vC);
         else o += sC;
         __builtin_amdgcn_sched_barrier(0);             // the second chain is issued before the barrier: its operands die in this step
@@ -329,47 +281,12 @@ __global__ __launch_bounds__(64 * NW, 2) void attention_x6_kernel(AttnArgs a) {
         if (have) front();
         barrier_lds();                           // the final states below re-use the staging image
         if (have) {
-            if (tail_keys && kb == lay.P - 1) mask_tail(kb, sC);
-            softmax(sC);
+            if (tail_keys && kb == lay.P - 1) mask_tail(kb, a.S, lh, sC);
+            softmax_step(sC, o, m_run, l_run);
             pv(sC, vC);
         }
     }
 #undef COFI_X6_CHAIN
 
-    // ---- this wave's state -> LDS; the KPH phase waves of a query block are merged in a fixed order -> the block's slot
-    l_run += __shfl_xor(l_run, 32, 64);
-    if (lh == 0) {
-        s_m[wave * 32 + li] = m_run;
-        s_l[wave * 32 + li] = l_run;
-    }
-#pragma unroll
-    for (int rq = 0; rq < 4; ++rq)
-        *reinterpret_cast<float4 *>(&s_o[wave * 1024 + so_off(li, 2 * rq + lh)]) = make_float4(o[4 * rq], o[4 * rq + 1], o[4 * rq + 2], o[4 * rq + 3]);
-    __syncthreads();
-    {
-        const int qb = tid >> 8, q = (tid >> 3) & 31, ch = tid & 7;
-        const int blk = qsb * QG + qb;
-        if (blk < lay.QB) {
-            float mm = -1e30f;
-#pragma unroll
-            for (int p = 0; p < KPH; ++p) mm = fmaxf(mm, s_m[(p * QG + qb) * 32 + q]);
-            float l = 0.f;
-            float4 r = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-            for (int p = 0; p < KPH; ++p) {
-                const int w = p * QG + qb;
-                const float sc = fast_exp2(s_m[w * 32 + q] - mm);
-                l += s_l[w * 32 + q] * sc;
-                const float4 t = *reinterpret_cast<const float4 *>(&s_o[w * 1024 + so_off(q, ch)]);
-                r.x += t.x * sc; r.y += t.y * sc; r.z += t.z * sc; r.w += t.w * sc;
-            }
-            const int pair = fh * lay.QB + blk;
-            float *slot = a.parts + ((size_t)pair * lay.KS + ks) * COFI_ATTN_SLOT_FLOATS;
-            if (ch == 0) {
-                slot[q] = mm;
-                slot[32 + q] = l;
-            }
-            *reinterpret_cast<float4 *>(slot + 64 + q * 32 + 4 * ch) = r;
-        }
-    }
+    store_slot(a, u, wave, li, lh, o, m_run, l_run, s_m, s_l, s_o);
 }

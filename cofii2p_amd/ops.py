@@ -1176,37 +1176,41 @@ def attention_arith() -> str:
     return "f32" if gemm_mode() == "f32" else "bf16x6"
 
 
+def _attn_operands(what: str, q, k, v, nhead: int, frames: int):
+    """q (frames*L, HD), k / v (frames*S, HD) of an attention call, judged by tensor metadata before anything is launched: the kernels
+    read k and v by the rows of k and every operand by nhead heads of D = HD / nhead columns, without bounds of their own.  -> L, S (rows
+    per frame) and D."""
+    _mat(q, "q"), _mat(k, "k", device=q.device), _mat(v, "v", device=q.device)
+    L, HD = q.shape
+    S = k.shape[0]
+    if nhead <= 0 or k.shape[1] != HD or tuple(v.shape) != (S, HD) or HD % nhead:
+        raise _lib.CofiError("%s: q %s, k %s, v %s do not hold %d heads of one width" % (what, tuple(q.shape), tuple(k.shape), tuple(v.shape), nhead))
+    if frames <= 0 or L % frames or S % frames:
+        raise _lib.CofiError("%s: rows are not a multiple of the frame count" % what)
+    return L // frames, S // frames, HD // nhead
+
+
 def attention_parts(q, k, v, q_colscale=None, nhead: int = 4, frames: int = 1, q_colpart=None, q_eps: float = 1e-12) -> "AttnParts":
     """The attention kernel itself (cofi_attention_parts): -> the partial slots (AttnParts) in a per-stream workspace.
     Stack mode: q (frames*L, HD), k/v (frames*S, HD), q_colscale (frames, HD).  q_colpart (nslab, ncols, 2): the column
     partials of the GEMM / fused tail that produced q (its first HD columns) - the token-axis norm of Q is then folded inside the kernel."""
     lib = _lib.load()
-    _mat(q, "q"), _mat(k, "k"), _mat(v, "v")
-    L, HD = q.shape
-    S = k.shape[0]
-    D = HD // nhead
-    if L % frames or S % frames:
-        raise _lib.CofiError("attention: rows are not a multiple of the frame count")
-    L, S = L // frames, S // frames
+    L, S, D = _attn_operands("attention", q, k, v, nhead, frames)
     nbytes = lib.cofi_attention_workspace(L, S, nhead, D, frames)
     if nbytes == 0:
         raise _lib.CofiError("attention: unsupported shape (head dimension must be 32)")
     # the slot table outlives this call when it is handed to the consumer: a per-stream workspace is safe (stream ordered)
     ws = _WS_ATTN.get(nbytes, q.device)
+    tail = (_p(q_colscale), _p(q_colpart), 0 if q_colpart is None else q_colpart.shape[0], 0 if q_colpart is None else q_colpart.shape[1], q_eps,
+            L, S, nhead, D, 1.0 / math.sqrt(D), frames, _p(ws), ws.numel(), _stream())
     if attention_arith() == "bf16x6" and 0 < ATTN_PRESPLIT_ROWS <= L:
         pb = lib.cofi_attention_kv_planes_bytes(S, nhead, D, frames)
         img = _WS_ATTN_KV.get(pb, q.device)
         _lib.check(lib.cofi_attention_kv_planes(_p(k), _ld(k), _p(v), _ld(v), S, nhead, D, frames, _p(img), img.numel(), _stream()), "cofi_attention_kv_planes")
-        rc = lib.cofi_attention_parts_planes(_p(q), _ld(q), _p(img), img.numel(), _p(q_colscale), _p(q_colpart),
-                                             0 if q_colpart is None else q_colpart.shape[0], 0 if q_colpart is None else q_colpart.shape[1], q_eps,
-                                             L, S, nhead, D, 1.0 / math.sqrt(D), frames, _p(ws), ws.numel(), _stream())
-        _lib.check(rc, "cofi_attention_parts_planes")
-        return AttnParts(ws, L, S, nhead, D, frames)
-    fn = lib.cofi_attention_parts_bf16x6 if attention_arith() == "bf16x6" else lib.cofi_attention_parts
-    rc = fn(_p(q), _ld(q), _p(k), _ld(k), _p(v), _ld(v), _p(q_colscale), _p(q_colpart),
-            0 if q_colpart is None else q_colpart.shape[0], 0 if q_colpart is None else q_colpart.shape[1], q_eps,
-            L, S, nhead, D, 1.0 / math.sqrt(D), frames, _p(ws), ws.numel(), _stream())
-    _lib.check(rc, "cofi_attention_parts")
+        _lib.check(lib.cofi_attention_parts_planes(_p(q), _ld(q), _p(img), img.numel(), *tail), "cofi_attention_parts_planes")
+    else:
+        fn = lib.cofi_attention_parts_bf16x6 if attention_arith() == "bf16x6" else lib.cofi_attention_parts
+        _lib.check(fn(_p(q), _ld(q), _p(k), _ld(k), _p(v), _ld(v), *tail), "cofi_attention_parts")
     return AttnParts(ws, L, S, nhead, D, frames)
 
 
@@ -1227,15 +1231,8 @@ def linear_attention(q, k, v, q_colscale=None, q_colpart=None, nhead: int = 4, f
     q_colpart (nslab, ncols, 2): the column partials of the GEMM / fused tail that produced q (its first HD columns), turned into the
     per-frame token-axis scale by cofi_col_inv_norm_from_colpart (slabs must not straddle frames).  fp32 FMA whatever COFI_GEMM / COFI_ATTN say."""
     lib = _lib.load()
-    _mat(q, "q"), _mat(k, "k", device=q.device), _mat(v, "v", device=q.device)
-    L, HD = q.shape
-    S = k.shape[0]
-    if k.shape[1] != HD or tuple(v.shape) != (S, HD) or HD % nhead:
-        raise _lib.CofiError("linear_attention: q %s, k %s, v %s do not hold %d heads of one width" % (tuple(q.shape), tuple(k.shape), tuple(v.shape), nhead))
-    D = HD // nhead
-    if L % frames or S % frames:
-        raise _lib.CofiError("linear_attention: rows are not a multiple of the frame count")
-    L, S = L // frames, S // frames
+    L, S, D = _attn_operands("linear_attention", q, k, v, nhead, frames)
+    HD = q.shape[1]
     nbytes = lib.cofi_linear_attention_workspace(L, S, nhead, D, frames)
     if nbytes == 0:
         raise _lib.CofiError("linear_attention: unsupported shape (head dimension must be 32)")

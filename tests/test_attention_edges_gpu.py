@@ -9,7 +9,7 @@ Measured on an MI355X (256 compute units; the cases run KS = 1 .. 8), largest ke
                      flat   peaked  sentinel_up  sentinel_down  v_1e4  v_1e-4
     bf16x6           0.30   0.28    0.20         0.22           0.29   0.30     (presplit: the same bits)
     f32              0.31   0.28    0.26         0.33           0.38   0.30
-A build whose tail mask keeps key S (">" for ">=" in mask_tail of both kernels) fails 399 of the 480 tests of this file."""
+A build whose tail mask keeps key S (">" for ">=" in mask_tail, then written out in both kernels) fails 399 of the 480 tests of this file."""
 import ctypes
 
 import pytest
@@ -260,6 +260,22 @@ def test_head_dimension_leading_dimension_and_alignment_are_refused(attn):
     assert lib.cofi_attention_merge(p(ws), ws.numel(), 48, 80, 4, 32, 1, p(out), 96, None) == L_.COFI_EINVAL
     torch.cuda.synchronize()
     assert bool((out == 7.0).all())
+
+
+def test_attention_operand_refusals(ops):
+    """Operands that do not fit each other are refused from their metadata, before anything is launched, by the softmax and the linear
+    attention alike (ops._attn_operands): the kernels read k and v by the rows of k and nhead heads of HD / nhead columns unchecked"""
+    CofiError = _lib().CofiError
+    q, k, v = (torch.zeros(n, 128, device=DEV) for n in (40, 50, 50))
+    bad = {"k of width 96": dict(k=torch.zeros(50, 96, device=DEV)), "v of shape (49, 128)": dict(v=torch.zeros(49, 128, device=DEV)),
+           "nhead = 3": dict(nhead=3), "frames = 3": dict(frames=3), "k on the CPU": dict(k=torch.zeros(50, 128))}
+    for fn in (ops.attention_parts, ops.linear_attention):
+        for what, change in bad.items():
+            kw = dict(q=q, k=k, v=v, nhead=4)
+            kw.update(change)
+            with pytest.raises(CofiError):
+                fn(**kw)
+                pytest.fail("%s accepted %s" % (fn.__name__, what))
 
 
 # ================================================================================================ the fused layer tail
