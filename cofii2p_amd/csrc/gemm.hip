@@ -513,6 +513,155 @@ __device__ __forceinline__ void rowwise_epilogue(const GemmArgs &g, const float 
     rowwise_epilogue_pre<ROWS, BN, FROM_WS, NT>(g, tile, TLD, m0, n0, slab, red, ec, er);
 }
 
+// ------------------------------------------------------------------------------------------------------
+// The tail of gemm_planes_kernel and gemm_f16_big_kernel: what happens behind the K loop.  (gemm_kernel and gemm_bf16x3_kernel above / below
+// and gemm_x6_big_kernel in gemm_x6_big.inc end in copies of their own of the same code: calling the shared form from them measured
+// 0.2 - 0.8 % slower over their probes - 1 - 13 % per launch for the ANORM / CONV instantiations of gemm_x6_big_kernel -, outside the
+// parent's run-to-run range: profiles/gemm_tail/README.md.  A change to the lean slab loop below has to be made in gemm_x6_big.inc as well.)
+// Both hold the result as 32 x 32 MFMA tiles acc[TM][TN] in a wave grid, wave (wm, wn) owning rows
+// wm * 32 TM .. and columns wn * 32 TN .. of the tile at (m0, n0); lane (li = lane & 31, lh = lane >> 5) holds in acc[i][j][r] the element
+// at row (r & 3) + 8 * (r >> 2) + 4 * lh, column li of its 32 x 32 tile (the D layout).  `lds` is the workgroup's operand storage, re-used
+// as a row-major fp32 slab of leading dimension BN + 4 (and as the scratch of the column-statistics fold).
+
+// split-K: raw partial sums straight from the D layout into slice z of the workspace
+template <int TM, int TN>
+__device__ __forceinline__ void mfma32_store_partial(const GemmArgs &g, const f32x16 (&acc)[TM][TN], int z, int m0, int n0, int wm, int wn, int li, int lh) {
+#pragma unroll
+    for (int i = 0; i < TM; ++i)
+#pragma unroll
+        for (int j = 0; j < TN; ++j) {
+            const int col = n0 + wn * 32 * TN + j * 32 + li;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int row = m0 + wm * 32 * TM + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+                if (row < g.M && col < g.N) g.ws[((size_t)z * g.M + row) * g.N + col] = acc[i][j][r];
+            }
+        }
+}
+
+// the 32-row blocks of 64-row slab h of the tile -> row-major LDS slab (waves that hold none of them write nothing)
+template <int BN, int TM, int TN>
+__device__ __forceinline__ void mfma32_slab_to_lds(const f32x16 (&acc)[TM][TN], float *lds, int h, int wm, int wn, int li, int lh) {
+    constexpr int TLD = BN + 4;
+#pragma unroll
+    for (int i = 0; i < TM; ++i) {
+        const int rb = wm * TM + i;   // 32-row block of the tile held in acc[i][*]
+        if ((rb >> 1) == h) {
+#pragma unroll
+            for (int j = 0; j < TN; ++j)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int rl = (rb & 1) * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+                    lds[rl * TLD + wn * 32 * TN + j * 32 + li] = acc[i][j][r];
+                }
+        }
+    }
+}
+
+// Tail of the kernels whose K loop does not end on a barrier (gemm_planes_kernel: LEAN = false; gemm_f16_big_kernel: LEAN = true),
+// NT threads, 64-row slabs: split-K partial store, else the lean slab loop when its conditions hold, else barrier + generic
+// slab loop.
+template <int BM, int BN, int TM, int TN, int NT, bool LEAN>
+__device__ __forceinline__ void mfma32_tile_tail(const GemmArgs &g, const f32x16 (&acc)[TM][TN], float *lds, int z, int m0, int n0,
+                                                 int wm, int wn, int li, int lh, int tid) {
+    static_assert(BM % 64 == 0, "64-row slabs");
+    constexpr int TLD = BN + 4;
+    if (g.ksplit > 1) {
+        mfma32_store_partial<TM, TN>(g, acc, z, m0, n0, wm, wn, li, lh);
+        return;
+    }
+    // LEAN epilogue (no fused LayerNorm / L2 normalisation / sigmoid, whole float4 columns inside N, aligned output - every launch of the
+    // forward that takes the f16x3 kernel): straight-line code per slab, every decision uniform and taken once.  vmcnt counts stores as well
+    // as loads: a load issued behind the stores of a slab makes its consumer wait for their round trip (and a wait the compiler places on a
+    // path that happens to have no load at all still drains the stores) - four store round trips per tile otherwise.  So: bias and the row
+    // divisors of the whole tile are loaded BEFORE the slab loop, which then holds no load at all; only a residual is loaded per slab, one
+    // slab ahead of its use (before the stores of the slab in between).  Same operations in the same order as rowwise_epilogue: same bits.
+    if constexpr (LEAN) {
+    const bool vec_ok = ((g.N & 3) == 0) && ((g.ldc & 3) == 0) && ((reinterpret_cast<uintptr_t>(g.C) & 15) == 0);
+    const bool res_ok = !g.res || (((g.ldr & 3) == 0) && ((reinterpret_cast<uintptr_t>(g.res) & 15) == 0));
+    if (!g.ln_gamma && !g.l2n && vec_ok && res_ok && n0 + BN <= g.N && g.act != COFI_ACT_SIGMOID) {
+        constexpr int TPR = BN / 4, RPP = NT / TPR, NP = 64 / RPP, NS = BM / 64;   // 256 threads, BN = 128: 32 threads per row, 8 rows per pass, 8 passes per slab
+        const int tc = tid % TPR, tr = tid / TPR;
+        const int col = n0 + 4 * tc;
+        const bool has_stats = g.colpart != nullptr;
+        float bias4[4] = {0.f, 0.f, 0.f, 0.f};
+        if (g.bias) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) bias4[e] = g.bias[col + e];
+        }
+        float rd[NS][NP];
+#pragma unroll
+        for (int h = 0; h < NS; ++h)
+#pragma unroll
+            for (int p = 0; p < NP; ++p) rd[h][p] = 1.0f;
+        if (g.rowdiv) {
+#pragma unroll
+            for (int h = 0; h < NS; ++h)
+#pragma unroll
+                for (int p = 0; p < NP; ++p) rd[h][p] = g.rowdiv[min(m0 + 64 * h + p * RPP + tr, g.M - 1)];   // rows past M are never stored
+        }
+        auto run = [&](auto with_res) __attribute__((always_inline)) {
+            constexpr bool RES = decltype(with_res)::value;
+            float rs[NP][4], rs_next[NP][4];
+#pragma unroll
+            for (int p = 0; p < NP; ++p)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) rs[p][e] = rs_next[p][e] = 0.f;
+            auto load_res = [&](int h, float (&dst)[NP][4]) __attribute__((always_inline)) {
+                if constexpr (RES) load_res_slab<NP, RPP>(g, m0 + 64 * h + tr, col, dst);
+            };
+            load_res(0, rs);
+            __syncthreads();   // every wave is done with the operand stages
+#pragma unroll
+            for (int h = 0; h < NS; ++h) {
+                const bool live = m0 + 64 * h < g.M;   // uniform: no statistics slab (and no rows) behind the last valid row
+                if (live) mfma32_slab_to_lds<BN, TM, TN>(acc, lds, h, wm, wn, li, lh);
+                __syncthreads();
+                if (h + 1 < NS) load_res(h + 1, rs_next);
+                float cs[4] = {0.f, 0.f, 0.f, 0.f}, cq[4] = {0.f, 0.f, 0.f, 0.f};
+                if (live) {
+                    float x[NP][4];
+#pragma unroll
+                    for (int p = 0; p < NP; ++p) {
+                        const f32x4 t = *reinterpret_cast<const f32x4 *>(lds + (p * RPP + tr) * TLD + 4 * tc);
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) x[p][e] = t[e];
+                    }
+                    epi_fast_apply<NP, RPP, RES>(g, x, bias4, rd[h], rs, col, m0 + 64 * h + tr, cs, cq);
+                }
+                // every thread passes the same number of barriers whether the slab is live or dead: colstat_fold holds one, the dead
+                // branch pairs it
+                if (has_stats) {   // uniform.  Fold of the RPP row phases in a fixed order, as rowwise_epilogue
+                    __syncthreads();
+                    if (live) colstat_fold<BN, RPP>(g, lds, cs, cq, (m0 >> 6) + h, n0, tr, tc);
+                    else __syncthreads();
+                }
+                __syncthreads();
+                if constexpr (RES) {
+#pragma unroll
+                    for (int p = 0; p < NP; ++p)
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) rs[p][e] = rs_next[p][e];
+                }
+            }
+        };
+        if (g.res) run(std::true_type{});
+        else run(std::false_type{});
+        return;
+    }
+    }
+    // generic path: rowwise_epilogue per slab (loads its own operands); the stages are dead after the barrier
+    __syncthreads();
+#pragma unroll
+    for (int h = 0; h < BM / 64; ++h) {
+        if (m0 + 64 * h >= g.M) break;   // uniform: no statistics slab (and no rows) behind the last valid row
+        mfma32_slab_to_lds<BN, TM, TN>(acc, lds, h, wm, wn, li, lh);
+        __syncthreads();
+        rowwise_epilogue<64, BN, false, NT>(g, lds, TLD, m0 + 64 * h, n0, (m0 >> 6) + h, lds);
+        __syncthreads();
+    }
+}
+
 template <int BM, int BN, int TM, int TN>
 __global__ __launch_bounds__(256) void gemm_kernel(GemmArgs g) {
     static_assert(BM == 64 * TM && BN == 64 * TN, "2x2 waves");

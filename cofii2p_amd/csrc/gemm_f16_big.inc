@@ -26,8 +26,8 @@
 // The accumulators carry the factor sA sW; the epilogue (and the split-K partial store) multiplies by its reciprocal first - exact.
 //
 // Loop, tile geometry, LDS image (64-byte plane rows, 16-byte chunks XOR-swizzled by (row >> 2) & 3), operand forms (dense A,
-// implicit 3 x 3 convolution, pending normalisation of A), split-K partials, epilogue and XCD tile order are those of
-// gemm_x6_big_kernel; two planes instead of three: 2 x 48 KB of LDS, 96 fragment registers.  The split of four values is 12 vector
+// implicit 3 x 3 convolution, pending normalisation of A) and XCD tile order are those of gemm_x6_big_kernel, the tail behind the K loop
+// is the shared one (gemm.hip, mfma32_tile_tail with its lean slab loop); two planes instead of three: 2 x 48 KB of LDS, 96 fragment registers.  The split of four values is 12 vector
 // instructions (8 v_fma_mixlo/hi_f16: each half of hi and of lo is one fused multiply-add rounded to fp16 - the f16 operand of the residual
 // read in place -, 2 more for the second hi half as an operand, 2 v_max3_f32) against 22 of the three-plane bf16 split; a static W arrives
 // pre-split (WPRE below) and costs none.
@@ -652,115 +652,6 @@ __global__ __launch_bounds__(64 * NW, BM_ == 128 ? 2 : NW / 4) void gemm_f16_big
             for (int j = 0; j < TN; ++j) acc[i][j] *= inv;
     }
 
-    const int lix = li, lhx = lh;
-    if (g.ksplit > 1) {
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-            for (int j = 0; j < TN; ++j) {
-                const int col = n0 + wn * 32 * TN + j * 32 + lix;
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int row = m0 + wm * 32 * TM + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lhx;
-                    if (row < g.M && col < g.N) g.ws[((size_t)bid.z * g.M + row) * g.N + col] = acc[i][j][r];
-                }
-            }
-        return;
-    }
-    // ---- epilogue in 64-row slabs through LDS (as gemm_x6_big_kernel)
-    float *lds = reinterpret_cast<float *>(lds_raw);
-    auto slab_to_lds = [&](int h) __attribute__((always_inline)) {
-#pragma unroll
-        for (int i = 0; i < TM; ++i) {
-            const int rb = wm * TM + i;
-            if ((rb >> 1) == h) {
-#pragma unroll
-                for (int j = 0; j < TN; ++j)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) {
-                        const int rl = (rb & 1) * 32 + (r & 3) + 8 * (r >> 2) + 4 * lhx;
-                        lds[rl * TLD + wn * 32 * TN + j * 32 + lix] = acc[i][j][r];
-                    }
-            }
-        }
-    };
-    const bool vec_ok = ((g.N & 3) == 0) && ((g.ldc & 3) == 0) && ((reinterpret_cast<uintptr_t>(g.C) & 15) == 0);
-    const bool res_ok = !g.res || (((g.ldr & 3) == 0) && ((reinterpret_cast<uintptr_t>(g.res) & 15) == 0));
-    if (!g.ln_gamma && !g.l2n && vec_ok && res_ok && n0 + BN <= g.N && g.act != COFI_ACT_SIGMOID) {
-        constexpr int TPR = BN / 4, RPP = NT / TPR, NP = 64 / RPP, NS = BM / 64;
-        const int tc = tid % TPR, tr = tid / TPR;
-        const int col = n0 + 4 * tc;
-        const bool has_stats = g.colpart != nullptr;
-        float bias4[4] = {0.f, 0.f, 0.f, 0.f};
-        if (g.bias) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) bias4[e] = g.bias[col + e];
-        }
-        float rdv[NS][NP];
-#pragma unroll
-        for (int h = 0; h < NS; ++h)
-#pragma unroll
-            for (int p = 0; p < NP; ++p) rdv[h][p] = 1.0f;
-        if (g.rowdiv) {
-#pragma unroll
-            for (int h = 0; h < NS; ++h)
-#pragma unroll
-                for (int p = 0; p < NP; ++p) rdv[h][p] = g.rowdiv[min(m0 + 64 * h + p * RPP + tr, g.M - 1)];
-        }
-        auto run = [&](auto with_res) __attribute__((always_inline)) {
-            constexpr bool RES = decltype(with_res)::value;
-            float rs[NP][4], rs_next[NP][4];
-#pragma unroll
-            for (int p = 0; p < NP; ++p)
-#pragma unroll
-                for (int e = 0; e < 4; ++e) rs[p][e] = rs_next[p][e] = 0.f;
-            auto load_res = [&](int h, float (&dst)[NP][4]) __attribute__((always_inline)) {
-                if constexpr (RES) load_res_slab<NP, RPP>(g, m0 + 64 * h + tr, col, dst);
-            };
-            load_res(0, rs);
-            __syncthreads();   // every wave is done with the operand stages
-#pragma unroll
-            for (int h = 0; h < NS; ++h) {
-                const bool live = m0 + 64 * h < g.M;
-                if (live) slab_to_lds(h);
-                __syncthreads();
-                if (h + 1 < NS) load_res(h + 1, rs_next);
-                float cs[4] = {0.f, 0.f, 0.f, 0.f}, cq[4] = {0.f, 0.f, 0.f, 0.f};
-                if (live) {
-                    float x[NP][4];
-#pragma unroll
-                    for (int p = 0; p < NP; ++p) {
-                        const f32x4 t = *reinterpret_cast<const f32x4 *>(lds + (p * RPP + tr) * TLD + 4 * tc);
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) x[p][e] = t[e];
-                    }
-                    epi_fast_apply<NP, RPP, RES>(g, x, bias4, rdv[h], rs, col, m0 + 64 * h + tr, cs, cq);
-                }
-                if (has_stats) {
-                    __syncthreads();
-                    if (live) colstat_fold<BN, RPP>(g, lds, cs, cq, (m0 >> 6) + h, n0, tr, tc);
-                    else __syncthreads();
-                }
-                __syncthreads();
-                if constexpr (RES) {
-#pragma unroll
-                    for (int p = 0; p < NP; ++p)
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) rs[p][e] = rs_next[p][e];
-                }
-            }
-        };
-        if (g.res) run(std::true_type{});
-        else run(std::false_type{});
-        return;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int h = 0; h < BM / 64; ++h) {
-        if (m0 + 64 * h >= g.M) break;
-        slab_to_lds(h);
-        __syncthreads();
-        rowwise_epilogue<64, BN, false, NT>(g, lds, TLD, m0 + 64 * h, n0, (m0 >> 6) + h, lds);
-        __syncthreads();
-    }
+    // ---- split-K partials, or the epilogue in 64-row slabs through LDS (lean where its conditions hold)
+    mfma32_tile_tail<BM, BN, TM, TN, NT, true>(g, acc, reinterpret_cast<float *>(lds_raw), bid.z, m0, n0, wm, wn, li, lh, tid);
 }

@@ -20,7 +20,8 @@
 //     applied to the per-lane SOURCE address (every instruction still covers whole 128-B / 64-B row segments).
 //   * K tails and nothing else need zero fill: lanes whose chunk starts past the K range read a 16-byte zero page instead.
 //     Rows past M / N are clamped to the last row (their results are never stored).
-// Epilogue, split-K partials and the XCD tile order are those of the other kernels (rowwise_epilogue, 64-row statistics slabs).
+// The tail behind the K loop is the shared one (gemm.hip, mfma32_tile_tail: split-K partials, else 64-row slabs through rowwise_epilogue);
+// the XCD tile order is that of the other kernels.
 
 __device__ __attribute__((aligned(16))) unsigned g_zero_chunk[4];   // zero-initialised: the source of K-tail chunks
 
@@ -218,42 +219,6 @@ __global__ __launch_bounds__(64 * WM * WN, MINW) void gemm_planes_kernel(GemmArg
         }
     }
 
-    if (g.ksplit > 1) {
-        // raw partial sums straight from the D layout: row = (r&3) + 8*(r>>2) + 4*(lane>>5), col = lane&31
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-            for (int j = 0; j < TN; ++j) {
-                const int col = n0 + wn * 32 * TN + j * 32 + li;
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int row = m0 + wm * 32 * TM + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-                    if (row < g.M && col < g.N) g.ws[((size_t)bid.z * g.M + row) * g.N + col] = acc[i][j][r];
-                }
-            }
-        return;
-    }
-    // ---- epilogue in 64-row slabs through LDS (the stages are dead after the barrier)
-    float *lds = reinterpret_cast<float *>(lds_raw);
-    __syncthreads();
-#pragma unroll
-    for (int h = 0; h < BM / 64; ++h) {
-        if (m0 + 64 * h >= g.M) break;   // uniform: no statistics slab (and no rows) behind the last valid row
-#pragma unroll
-        for (int i = 0; i < TM; ++i) {
-            const int rb = wm * TM + i;   // 32-row block of the tile held in acc[i][*]
-            if ((rb >> 1) == h) {
-#pragma unroll
-                for (int j = 0; j < TN; ++j)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) {
-                        const int rl = (rb & 1) * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-                        lds[rl * TLD + wn * 32 * TN + j * 32 + li] = acc[i][j][r];
-                    }
-            }
-        }
-        __syncthreads();
-        rowwise_epilogue<64, BN, false, NT>(g, lds, TLD, m0 + 64 * h, n0, (m0 >> 6) + h, lds);
-        __syncthreads();
-    }
+    // ---- split-K partials, or the epilogue in 64-row slabs through LDS
+    mfma32_tile_tail<BM, BN, TM, TN, NT, false>(g, acc, reinterpret_cast<float *>(lds_raw), bid.z, m0, n0, wm, wn, li, lh, tid);
 }

@@ -333,6 +333,8 @@ __global__ __launch_bounds__(256, 1) void gemm_x6_big_kernel(GemmArgs g) {
             }
         }
     };
+    // (this tail is a copy of mfma32_tile_tail<..., LEAN = true> of gemm.hip, kept here because the shared form measured slower in this kernel:
+    // a change to one has to be made in the other)
     // LEAN epilogue (no fused LayerNorm / L2 normalisation / sigmoid, whole float4 columns inside N, aligned output - every launch of the
     // forward that takes this kernel): straight-line code per slab, every decision uniform and taken once.  vmcnt counts stores as well as
     // loads: a load issued behind the stores of a slab makes its consumer wait for their round trip (and a wait the compiler places on a
