@@ -163,6 +163,7 @@ SIGNATURES = {
     "cofi_match_finish_rig": (_I, [_P, _P, _I, _P, _P, _I, _P, _I, _I, _I, _I, _P, _I, _F, _P, _I, _P, _P, _P, _I, _P, _P, _I, _I, _I, _P]),
     "cofi_repeat_frames": (_I, [_P, _I, _I, _I, _I, _I, _P, _I, _P]),
     "cofi_fine_match": (_I, [_P, _P, _I, _I, _P, _I, _F, _P, _I, _P, _P, _P]),
+    "cofi_fine_refine": (_I, [_P, _I, _I, _I, _I, _P, _I, _F, _P, _I, _P, _P, _I, _P, _P, _I, _P]),
     "cofi_kpconv_fused_slab_rows": (_I, [_I, _I, _I]),
     "cofi_kpconv_fused": (_I, [_P, _I, _I, _I, _P, _P, _P, _I, _I, _P, _F, _P, _P, _I, _P, _P, _I, _P, _I, _I, _P, _P]),
     "cofi_kpconv_fused_rec": (_I, [_P, _I, _I, _I, _P, _P, _P, _I, _I, _P, _F, _P, _I, _P, _P, _I, _P, _I, _I, _P, _P]),

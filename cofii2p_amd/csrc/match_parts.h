@@ -89,6 +89,68 @@ __device__ __forceinline__ int argmax16(float sim, int lane) {
     return bi;
 }
 
+// Cosine similarity (the rule of fine_cosine16: each norm clamped at 1e-8) of NR rows of C floats against one descriptor row, by one
+// wave.  rows[p] == nullptr (the same in every lane) stands for a row that is not read; its similarity is 0.  Lane l owns channels
+// 4 l .. 4 l + 3, then + 256, ...: one 16-byte load per row and round where vec allows it (every row pointer 16-byte aligned; a round
+// that ends past C is read float by float), and the SAME channels in the same order where it does not, so a lane's sums - and with the
+// fixed butterfly the similarity - do not depend on vec, and rows that hold equal values give bit-equal similarities.
+template <int NR>
+__device__ __forceinline__ void cosine_rows(const float *const (&rows)[NR], const float *feat, int C, bool vec, int lane, float (&sim)[NR]) {
+    float dot[NR], nn[NR], pp = 0.f;
+#pragma unroll
+    for (int p = 0; p < NR; ++p) dot[p] = nn[p] = 0.f;
+    for (int c0 = 4 * lane; c0 < C; c0 += 256) {
+        float fv[4], pv[NR][4];
+        if (vec && c0 + 4 <= C) {
+            const float4 t = *reinterpret_cast<const float4 *>(feat + c0);
+            fv[0] = t.x; fv[1] = t.y; fv[2] = t.z; fv[3] = t.w;
+#pragma unroll
+            for (int p = 0; p < NR; ++p) {
+                const float4 v = rows[p] ? *reinterpret_cast<const float4 *>(rows[p] + c0) : make_float4(0.f, 0.f, 0.f, 0.f);
+                pv[p][0] = v.x; pv[p][1] = v.y; pv[p][2] = v.z; pv[p][3] = v.w;
+            }
+        } else {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const bool in = c0 + k < C;
+                fv[k] = in ? feat[c0 + k] : 0.f;
+#pragma unroll
+                for (int p = 0; p < NR; ++p) pv[p][k] = in && rows[p] ? rows[p][c0 + k] : 0.f;
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            pp += fv[k] * fv[k];
+#pragma unroll
+            for (int p = 0; p < NR; ++p) {
+                dot[p] += pv[p][k] * fv[k];
+                nn[p] += pv[p][k] * pv[p][k];
+            }
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        pp += __shfl_xor(pp, o, 64);
+#pragma unroll
+        for (int p = 0; p < NR; ++p) {
+            dot[p] += __shfl_xor(dot[p], o, 64);
+            nn[p] += __shfl_xor(nn[p], o, 64);
+        }
+    }
+    const float ny = fmaxf(sqrtf(pp), 1e-8f);
+#pragma unroll
+    for (int p = 0; p < NR; ++p) sim[p] = dot[p] / (fmaxf(sqrtf(nn[p]), 1e-8f) * ny);
+}
+// Offset in [-0.5, 0.5] of the peak of the parabola through the similarities sm, s0, sp at -1, 0, +1.  Where the three are not
+// strictly concave the offset is half a cell towards the larger neighbour, 0 between equal ones.  Every comparison is false for a NaN:
+// one among the three yields 0, and the clamp returns its bound where the quotient is one (Inf / Inf) - the result is always finite.
+__device__ __forceinline__ float parabola_offset(float sm, float s0, float sp) {
+    const float den = (sm - 2.0f * s0) + sp;
+    if (den < 0.f) return fminf(fmaxf(0.5f * (sm - sp) / den, -0.5f), 0.5f);
+    if (!(den >= 0.f)) return 0.f;
+    return sp > sm ? 0.5f : (sp < sm ? -0.5f : 0.f);
+}
+
 // One chunk of an ordered compaction by a workgroup of NW waves: thread (wave, lane) holds the chunk's element 64 wave + lane, kept
 // where ok.  store(slot) runs for every kept element, slots ascending from base in element order; base advances by the chunk's count.
 // s_cnt: NW ints of LDS.  All threads call; ends on a barrier (s_cnt reusable, the stores visible to the workgroup).

@@ -197,7 +197,63 @@ __global__ __launch_bounds__(256) void match_finish_kernel(FinishArgs a) {
     }
 }
 
+// Sub-pixel refinement of the fine matches match_finish left: one wave per match i of frame f, REF_NW matches per
+// workgroup.  The matched cell is the GEOMETRIC decode of best - column left + best % 4, row top + best / 4 of the fine map (fine_xy
+// keeps the reference caller's transposed one) - and each axis gets the peak of the parabola through the cosine similarities of the
+// descriptor with the cell and its two neighbours ON THE MAP, not in the patch.  No LDS, no barrier: a wave at or beyond the count
+// leaves at once.
+struct RefineArgs {
+    const float *fmap, *xy, *fpc;
+    const int32_t *best, *count;
+    float *sub_xy, *peak;
+    int ldf, C, H2, W2, ldxy, ldp, cap, vec;
+    float cscale;
+    int nb;   // workgroups per frame
+};
+constexpr int REF_NW = 4;
+
+__global__ __launch_bounds__(64 * REF_NW) void fine_refine_kernel(RefineArgs a) {
+    const int f = blockIdx.x / a.nb, i = (blockIdx.x - f * a.nb) * REF_NW + (int)(threadIdx.x >> 6);
+    if (i >= min(a.count[2 * f], a.cap)) return;   // wave-uniform
+    const int lane = threadIdx.x & 63;
+    a.fmap += (size_t)f * a.H2 * a.W2 * a.ldf; a.xy += (size_t)f * 2 * a.ldxy; a.fpc += (size_t)f * a.cap * a.ldp;
+    a.best += (size_t)f * a.cap; a.sub_xy += (size_t)f * 2 * a.cap; a.peak += (size_t)f * a.cap;
+    const int bi = a.best[i];
+    const int px = patch_origin(a.xy[i], a.cscale) + bi % 4, py = patch_origin(a.xy[a.ldxy + i], a.cscale) + bi / 4;
+    float dx = 0.f, dy = 0.f, pk = 0.f;
+    if (px >= 0 && px < a.W2 && py >= 0 && py < a.H2) {   // else a zero-padded patch cell won: nothing to refine
+        const bool ax = px >= 1 && px <= a.W2 - 2, ay = py >= 1 && py <= a.H2 - 2;
+        const float *c = a.fmap + ((size_t)py * a.W2 + (size_t)px) * a.ldf;
+        const size_t up = (size_t)a.W2 * a.ldf;
+        const float *const rows[5] = {c, ax ? c - a.ldf : nullptr, ax ? c + a.ldf : nullptr, ay ? c - up : nullptr, ay ? c + up : nullptr};
+        float s[5];
+        cosine_rows<5>(rows, a.fpc + (size_t)i * a.ldp, a.C, a.vec != 0, lane, s);
+        if (ax) dx = parabola_offset(s[1], s[0], s[2]);
+        if (ay) dy = parabola_offset(s[3], s[0], s[4]);
+        pk = fabsf(s[0]) < INFINITY ? s[0] : 0.f;   // a NaN or Inf on the map must not reach the pose tail
+    }
+    if (lane == 0) {
+        a.sub_xy[i] = (float)px + dx;
+        a.sub_xy[a.cap + i] = (float)py + dy;
+        a.peak[i] = pk;
+    }
+}
+
 }  // namespace
+
+extern "C" int cofi_fine_refine(const float *fmap, int ldf, int C, int H2, int W2, const float *coarse_xy, int ldxy, float center_scale,
+                                const float *fine_pc, int ldp, const int32_t *best, const int32_t *count_dev, int cap, float *sub_xy,
+                                float *peak, int frames, cofi_stream_t stream) {
+    if (!fmap || !coarse_xy || !fine_pc || !best || !count_dev || !sub_xy || !peak) return COFI_EINVAL;
+    if (C <= 0 || H2 <= 0 || W2 <= 0 || cap <= 0 || frames <= 0 || ldf < C || ldp < C || ldxy < cap) return COFI_EINVAL;
+    const int nb = cofi_cdiv(cap, REF_NW);
+    if ((long long)nb * frames > 0x7fffffffLL) return COFI_EINVAL;
+    // 16-byte loads: both operands aligned and every row of either a whole number of 16-byte words after the first
+    const int vec = ((reinterpret_cast<uintptr_t>(fmap) | reinterpret_cast<uintptr_t>(fine_pc)) % 16 == 0 && ldf % 4 == 0 && ldp % 4 == 0) ? 1 : 0;
+    RefineArgs a{fmap, coarse_xy, fine_pc, best, count_dev, sub_xy, peak, ldf, C, H2, W2, ldxy, ldp, cap, vec, center_scale, nb};
+    hipLaunchKernelGGL(fine_refine_kernel, dim3(nb * frames), dim3(64 * REF_NW), 0, cofi_s(stream), a);
+    return cofi_launch_status();
+}
 
 extern "C" int cofi_match_finish_rig(const float *pts4, const float *pts1, int N1, const int32_t *sel, const int32_t *count_dev, int cap,
                                      const float *fmap, int ldf, int C, int H2, int W2, const float *coarse_xy, int ldxy, float center_scale,

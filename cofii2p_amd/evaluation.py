@@ -23,6 +23,7 @@ import numpy as np
 import torch
 
 from . import _lib, metrics, ops
+from .pose import image_points
 
 __all__ = ["EvalTable", "eval_monitors", "summarize", "evaluate", "ROW_COLUMNS"]
 
@@ -99,7 +100,7 @@ def eval_monitors(handle_or_operands, K, P_gt, table: EvalTable, row_index=None)
         o0 = h["out"][0]
         if "coarse_pts_all" not in o0:
             raise _lib.CofiError("eval_monitors reads the submission-wide outputs of match_finish (coarse_pts_all, ...)")
-        obj, img, count, coord_major = o0["coarse_pts_all"], o0["fine_xy_all"], o0["count_all"][:, 0], True
+        obj, img, count, coord_major = o0["coarse_pts_all"], image_points(h["out"]), o0["count_all"][:, 0], True
         pose, result = _pose12(h["pose"]), h["pose"]["result"]
     else:
         missing = [k for k in ("object_points", "image_points", "pose", "result") if k not in h]
@@ -192,12 +193,15 @@ def _save_frame(fb, directory, step, ticket, pyr, K, P):
     except RuntimeError:   # no matches at any threshold: an empty frame
         fine_xy, object_points, score = torch.zeros((2, 0)), torch.zeros((0, 3)), torch.zeros((1, 1, 0))
     pred_P = pose_matrix(R, t)   # identity when the pose failed
-    metrics.save_frame_result(directory, step, metrics.frame_result(P.detach().cpu().numpy(), pred_P, K.detach().cpu(), pyr["points"][1].cpu(),
-                                                                    pyr["points"][-1].cpu(), score, fine_xy, object_points))
+    result = metrics.frame_result(P.detach().cpu().numpy(), pred_P, K.detach().cpu(), pyr["points"][1].cpu(), pyr["points"][-1].cpu(), score,
+                                  fine_xy, object_points)
+    if fb.subpixel:   # asked for: the points pred_P was fitted to, next to the reference's fine_xy
+        result["sub_xy"] = fb.sub_xy(ticket).cpu() if fine_xy.shape[1] else torch.zeros((2, 0))
+    metrics.save_frame_result(directory, step, result)
 
 
 def evaluate(model, frames: Iterable[Dict], opt=None, batch: int = 16, streams: int = 4, pose_iterations: int = 10000,
-             result_dir: Optional[str] = None, thresholds=None, slot_base: int = 200, device=None) -> Dict[str, object]:
+             result_dir: Optional[str] = None, thresholds=None, slot_base: int = 200, device=None, subpixel: bool = False) -> Dict[str, object]:
     """eval_all.py:63-139 plus IR_RMSE.py and calc_result.py over `frames`: an iterable of data-side samples holding 'pc_data_dict', 'img',
     'K' (the camera matrix of the image the network sees) and 'P' (the reference's GT_P) - FrameLoader.complete samples, or batches of 1
     of the reference's DataLoader; equal sizes.  The frames go through `FrameBatcher(pose=True, eval_table=...)`: `batch` frames per
@@ -207,6 +211,8 @@ def evaluate(model, frames: Iterable[Dict], opt=None, batch: int = 16, streams: 
 
     result_dir: additionally write the reference's per-frame result files (%06d.npy, metrics.save_frame_result) there; this reads
     every frame's points and matches back and is off by default.  `opt` is accepted for the shape of `validate`; nothing is read from it.
+    subpixel=True: the pass runs on sub-pixel matches (FrameBatcher(subpixel=True), ops.fine_refine): poses, inlier ratios and residuals
+    are those of the refined points, and the result files gain "sub_xy" (2, n) next to the unchanged "fine_xy".
     A frame's tensors must stay unmodified until its stack has been submitted (`FrameBatcher.submit`).  The batcher of a configuration
     (batch, streams, slot_base, pose_iterations) stays on the module with its ring of stacks, so a later pass replays the same captured
     graphs; `model._eval_batchers.clear()` lets go of them."""
@@ -224,12 +230,12 @@ def evaluate(model, frames: Iterable[Dict], opt=None, batch: int = 16, streams: 
     try:
         # one batcher per configuration, kept on the module: its stacks are the static inputs of the slots' captured graphs, so a later
         # pass (the next epoch's evaluation) replays them instead of capturing new ones
-        key = (int(batch), int(streams), int(slot_base), int(pose_iterations), str(dev))
+        key = (int(batch), int(streams), int(slot_base), int(pose_iterations), str(dev)) + (("subpixel",) if subpixel else ())
         batchers = model.__dict__.setdefault("_eval_batchers", {})
         fb = batchers.get(key)
         if fb is None:
             fb = batchers[key] = FrameBatcher(model, batch=batch, streams=streams, slot_base=slot_base, pose=True, pose_iterations=pose_iterations,
-                                              eval_table=table)
+                                              eval_table=table, subpixel=bool(subpixel))
         fb.reset()   # a pass that ended in an exception may have left a partly filled stack
         fb.eval_table = table
         prev, cur = [], []   # result files: the frames of a stack are written while the next stack runs

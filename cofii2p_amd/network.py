@@ -292,7 +292,8 @@ class CoFiI2P(nn.Module):
 
     # ------------------------------------------------------------------ device-side forward (no host sync)
     def _run_device(self, P, points, neighbors, subsampling, upsampling, feats, img, mode, fine_center_kpt_coors,
-                    fine_pc_inline_index, taps=None, order=None, pc_first: bool = False, cameras: int = 1, sorted_tables: bool = False):
+                    fine_pc_inline_index, taps=None, order=None, pc_first: bool = False, cameras: int = 1, sorted_tables: bool = False,
+                    subpixel: bool = False):
         """Everything of network.py:74-161 that runs on the device.  Test-mode outputs are sized at
         capacity (N4 rows) with the match count left in device memory: capturable in a hipGraph.
 
@@ -306,8 +307,14 @@ class CoFiI2P(nn.Module):
         tensors hold S frames; the KPConv-FPN, the point MLP and the position encoding run once per cloud and the coarse point tokens are
         copied C times into the transformer's point stream (ops.repeat_frames).  From there on everything is per image, as in stack
         mode; the matching tail reads the points and fine descriptors of cloud f // C.  Outputs: B per-image records, laid out as a
-        stack-mode submission of B frames lays them out."""
+        stack-mode submission of B frames lays them out.
+
+        subpixel (mode='test'): the sub-pixel refinement of the fine matches (ops.fine_refine: one launch for all B frames right behind
+        match_finish, while the fine map is live) - per-frame "sub_xy" (2, cap) and "sub_peak" (cap,), outs[0]["sub_xy_all"] (B, 2, cap)
+        and outs[0]["fine_img_map"], the map it read."""
         dev = img.device
+        if subpixel and mode != "test":
+            raise ValueError("subpixel=True refines the fine matches of mode='test'; mode=%r has none" % (mode,))
         B = img.shape[0]
         if cameras != 1 and (mode != "test" or taps is not None):
             raise ValueError("a rig (cameras = %d > 1) serves mode='test' only (forward_async): mode=%r shares no cloud between images" % (cameras, mode))
@@ -409,6 +416,8 @@ class CoFiI2P(nn.Module):
             if C2 <= 128:   # coarse point, point2node, patch, fine descriptor and the caller's fine matching (eval_all.py:99-105): one launch
                 cpts, pat, fpcs, fxy, fbest = (t if B > 1 else t[None] for t in
                                                ops.match_finish(points[-1], points[1], sel, cnt, up2, H2, W2, xy, fine_pc, 4.0, frames=B, cameras=cameras))
+                if subpixel:   # every operand is per image: a rig needs nothing special
+                    sxy, spk = (t if B > 1 else t[None] for t in ops.fine_refine(up2, H2, W2, xy, fpcs, fbest, cnt, 4.0, frames=B))
         if val_batched:   # network.py:137-141 for all frames: one launch (cofi_val_gather), labels read in place
             K = fine_center_kpt_coors.shape[2]
             if tuple(fine_center_kpt_coors.shape) != (B, 2, K) or tuple(fine_pc_inline_index.shape) != (B, K):
@@ -434,6 +443,8 @@ class CoFiI2P(nn.Module):
             else:
                 if C2 <= 128:
                     o["coarse_pts"], o["patches"], o["fine_pc"], o["fine_xy"], o["fine_best"] = cpts[f], pat[f], fpcs[f], fxy[f], fbest[f]
+                    if subpixel:
+                        o["sub_xy"], o["sub_peak"] = sxy[f], spk[f]
                 else:
                     pts4, pts1 = points[-1][cl * N4:(cl + 1) * N4], points[1][cl * N1:(cl + 1) * N1]
                     o["coarse_pts"] = ops.gather_points_sel(pts4, sel[f], cnt[f])
@@ -441,12 +452,18 @@ class CoFiI2P(nn.Module):
                     o["patches"] = ops.extract_patches_nhwc(up2_f, H2, W2, xy[f], cnt[f], N4, 4.0)
                     o["fine_pc"] = ops.gather_rows_sel(fpc, node, cnt[f], N4)
                     o["fine_xy"], o["fine_best"] = ops.fine_match(o["patches"], o["fine_pc"], xy[f], cnt[f], 4.0)  # eval_all.py:99-105
+                    if subpixel:
+                        o["sub_xy"], o["sub_peak"] = ops.fine_refine(up2_f, H2, W2, xy[f], o["fine_pc"], o["fine_best"], cnt[f], 4.0)
                 o.update(sel=sel[f], coarse_xy=xy[f], count=cnt[f])
             outs.append(o)
         if test:
             outs[0]["count_all"] = cnt   # (B, 2): one device-to-host copy serves every frame of the submission
             if C2 <= 128:   # what a batched consumer of the matches reads in place (pose.solve_pnp_ransac_batch): (B, cap, 3), (B, 2, cap)
                 outs[0]["coarse_pts_all"], outs[0]["fine_xy_all"] = cpts, fxy
+                if subpixel:   # ... and what it reads instead of fine_xy_all (pose.image_points)
+                    outs[0]["sub_xy_all"] = sxy
+            if subpixel:   # the map the refinement read stays with the submission: (B * H2 * W2, C2) pixel-major, its second operand
+                outs[0]["fine_img_map"] = up2
         if val_batched:   # what the batched consumer (validation.val_monitors) reads in place, and the maps the gathers came from
             outs[0].update(patches_all=pat_all, fine_pc_all=fpc_all, img_desc_all=img_t, pc_desc_all=pc_t, pc_score_all=pc_score,
                            points4=points[-1], fine_img_map=up2, fine_pc_map=fine_pc)
@@ -472,7 +489,7 @@ class CoFiI2P(nn.Module):
         return self._capture
 
     def _graph_forward(self, P, inputs: ForwardInputs, mode, slot: int = 0, branch_mask: int = 7, inputs_stable: bool = False,
-                       cameras: int = 1):
+                       cameras: int = 1, subpixel: bool = False):
         def sig(t):
             if t is None:
                 return None
@@ -486,6 +503,8 @@ class CoFiI2P(nn.Module):
         # what the call itself fixes of the launch sequence, then every switch (routing_state), then the tensor signatures
         key = ("stable" if inputs_stable else "copy", mode, str(dev), slot, branch_mask, cameras, inputs.sorted_tables,
                self.compute_unused_image_maps) + routing_state() + tuple(sig(t) for t in tensors)
+        if subpixel:   # one launch more in the recording; the key of every other submission stays what it was
+            key += ("subpixel",)
         with ops.recording_scope(slot, branch_mask):   # the slot's scratch namespace; which intra-frame forks the capture records
             rec = self._graphs.get(key)
             if rec is None:
@@ -504,7 +523,7 @@ class CoFiI2P(nn.Module):
                     return self._run_device(P, static.points, static.neighbors, static.subsampling, static.upsampling, static.feats, static.img,
                                             mode, static.kpt, static.inl, taps=None, order=static.order or None,
                                             pc_first=ALTERNATE_ORDER and branch_mask == 0 and bool(slot & 1), cameras=cameras,
-                                            sorted_tables=static.sorted_tables)
+                                            sorted_tables=static.sorted_tables, subpixel=subpixel)
 
                 # warm-up AND capture run on one persistent stream, so every per-stream workspace is grown (in the
                 # ordinary allocator pool) before the capture starts and nothing is allocated for it inside
@@ -566,7 +585,7 @@ class CoFiI2P(nn.Module):
     @torch.no_grad()
     def forward_async(self, slot: int, pc_data_dict, img, mode: str = "test", inputs_stable: bool = False, pose_K=None,
                       pose_iterations: int = 10000, pose_seed: int = 0, eval_into=None, cameras: int = 1, rig_extrinsics=None, fuse_into=None,
-                      pose_cov=False):
+                      pose_cov=False, subpixel: bool = False):
         """Enqueue one test-mode forward on the CURRENT stream through the hipGraph of slot `slot` and return
         immediately (no host sync).  `img` (1,3,H,W) = one frame, or (B,3,H,W) with a stack-mode `pc_data_dict`
         (see stack_frames) = B frames through the same launches.  Slots own their static buffers and scratch, so
@@ -622,8 +641,21 @@ class CoFiI2P(nn.Module):
         entries, (S, ...), from pose.pose_covariance_rig in the rig's tangent space, and the per-image entries are the frame form at E_c o rig
         pose on that image's own rows.  True estimates the pixel variance from the residuals.  Refused before anything is enqueued:
         pose_cov without pose_K, a pixel noise that is not a finite number > 0.  With the default False nothing about the call, its handle,
-        its buffers or its launches changes."""
+        its buffers or its launches changes.
+
+        subpixel=True: sub-pixel fine matches (ops.fine_refine, INTEGRATION.md "Sub-pixel matches": one launch for all frames inside the
+        recorded forward, right behind match_finish).  handle["out"][f] gains "sub_xy" (2, cap) - column and row on the fine map of the
+        matched cell, decoded geometrically (best % 4, best // 4; fine_xy keeps the reference caller's transposed decode), plus a parabolic
+        offset in [-0.5, 0.5] per axis - and "sub_peak" (cap,), handle["out"][0] gains "sub_xy_all" (B, 2, cap) and "fine_img_map", the
+        (B * H2 * W2, C2) pixel-major fine image map the refinement read; rows at or beyond a frame's count are undefined.  Every reader of
+        the submission's image points (pose.image_points: the pose tail of frames and rigs, the covariance, eval_into, and fuse_into
+        through the poses) then works from sub_xy_all.  fine_xy, fine_best and what finish() returns stay bit for bit what they are.
+        Part of the recording's key.  Refused before anything is enqueued: any mode but 'test'.  With the default False nothing about the
+        call, its recordings, its handle or its launches changes."""
         B = img.shape[0] if img.dim() == 4 else 1
+        subpixel = bool(subpixel)
+        if subpixel and mode != "test":
+            raise ValueError("forward_async(subpixel=True) refines the fine matches of mode='test', got mode=%r" % (mode,))
         if pose_cov is not False and pose_cov is not None:
             if pose_K is None:
                 raise _lib.CofiError("forward_async(pose_cov=...): the covariance belongs to the pose tail - pass pose_K")
@@ -668,7 +700,7 @@ class CoFiI2P(nn.Module):
         # fork/join only adds join latency then — measured 254 vs 331 frames/s at two frames in flight)
         with ops.arithmetic(self.arithmetic):
             outs = self._graph_forward(self._pack(img.device), inputs, mode, slot=slot, branch_mask=self.async_branch_mask,
-                                       inputs_stable=inputs_stable, cameras=cameras)
+                                       inputs_stable=inputs_stable, cameras=cameras, subpixel=subpixel)
         own = self._slots.get((slot, str(img.device)))
         if own is None:
             own = self._slots[(slot, str(img.device))] = _Slot()

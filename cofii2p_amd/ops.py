@@ -1601,6 +1601,41 @@ def match_finish(pts4, pts1, sel, cnt, fmap, H2: int, W2: int, xy, fine_pc_all, 
     return coarse_pts, patches, fine_pc, fine_xy, best
 
 
+def fine_refine(fmap, H2: int, W2: int, coarse_xy, fine_pc, best, count, center_scale: float, frames: int = 1):
+    """Sub-pixel refinement of the fine matches (cofi_fine_refine), on the operands match_finish leaves: fmap
+    (frames * H2 * W2, C) pixel-major, coarse_xy (2, cap) with any leading dimension >= cap, fine_pc (cap, C) - the per-match descriptor
+    rows -, best (cap,) int32, count (2,) int32; with frames > 1 every one of them holds `frames` equal blocks ((frames, 2, cap),
+    (frames, cap, C), (frames, cap), (frames, 2)).  -> sub_xy (2, cap): column and row of the matched cell on the map (the geometric
+    decode best % 4, best // 4 - not fine_xy's) plus a parabolic offset in [-0.5, 0.5] per axis, and peak (cap,): the similarity at the
+    cell; both gain a leading frame axis with frames > 1.  Rows at or beyond a frame's count are not written."""
+    lib = _lib.load()
+    _mat(fmap, "fmap")
+    if frames < 1 or best.numel() % frames:
+        raise _lib.CofiError("fine_refine: best holds %d rows, no whole number of %d frames" % (best.numel(), frames))
+    cap, C, dev = best.numel() // frames, fmap.shape[1], fmap.device
+    pc = fine_pc.reshape(frames * cap, -1) if fine_pc.dim() == 3 else fine_pc
+    _mat(pc, "fine_pc", device=dev)
+    if not (_on(best, dev) and _on(count, dev) and _on(coarse_xy, dev)):
+        raise _lib.CofiError("fine_refine: best, count and coarse_xy must be on %s, the device of fmap" % dev)
+    if fmap.shape[0] != frames * H2 * W2 or tuple(pc.shape) != (frames * cap, C) or count.numel() != 2 * frames:
+        raise _lib.CofiError("fine_refine: shape mismatch: fmap %s for %d x %d x %d pixels, fine_pc %s, best %s, count %s"
+                             % (tuple(fmap.shape), frames, H2, W2, tuple(fine_pc.shape), tuple(best.shape), tuple(count.shape)))
+    if best.dtype != torch.int32 or count.dtype != torch.int32 or coarse_xy.dtype != torch.float32:
+        raise _lib.CofiError("fine_refine: best and count are int32, coarse_xy float32")
+    if not (best.is_contiguous() and count.is_contiguous()) or coarse_xy.stride(-1) != 1 or coarse_xy.shape[-2] != 2 or coarse_xy.shape[-1] < cap:
+        raise _lib.CofiError("fine_refine: contiguous best / count and coarse_xy (2, >= cap) with unit column stride expected")
+    ldxy = coarse_xy.stride(-2)
+    if ldxy < cap or (frames > 1 and (coarse_xy.dim() != 3 or coarse_xy.shape[0] != frames or coarse_xy.stride(0) != 2 * ldxy)):
+        raise _lib.CofiError("fine_refine: coarse_xy must be (frames, 2, ld) with ld >= cap and frames packed behind one another")
+    lead = () if frames == 1 else (frames,)
+    sub_xy = torch.empty(lead + (2, cap), dtype=torch.float32, device=dev)
+    peak = torch.empty(lead + (cap,), dtype=torch.float32, device=dev)
+    rc = lib.cofi_fine_refine(_p(fmap), _ld(fmap), C, H2, W2, _p(coarse_xy), ldxy, float(center_scale), _p(pc), _ld(pc), _p(best), _p(count),
+                              cap, _p(sub_xy), _p(peak), frames, _stream())
+    _lib.check(rc, "cofi_fine_refine")
+    return sub_xy, peak
+
+
 # ------------------------------------------------------------------------------------------ validation pass (csrc/validation.hip)
 def _label(t: torch.Tensor, name: str, shape, dtype) -> torch.Tensor:
     if not t.is_cuda or t.dtype != dtype or tuple(t.shape) != tuple(shape) or not t.is_contiguous():

@@ -440,6 +440,14 @@ def pose_covariance_rig(object_points: torch.Tensor, image_points: torch.Tensor,
                                     stat, sigma_px, coord_major)
 
 
+def image_points(outs) -> torch.Tensor:
+    """The image points (B, 2, cap), coordinate-major, that every consumer of a forward_async submission's matches reads - `outs` is
+    handle["out"]: the sub-pixel matches "sub_xy_all" where the submission has them (forward_async(subpixel=True)), else the
+    reference's "fine_xy_all".  The one place that choice is made: the pose tail, the covariance and the evaluation monitors ask here."""
+    o0 = outs[0]
+    return o0["sub_xy_all"] if "sub_xy_all" in o0 else o0["fine_xy_all"]
+
+
 class PoseTail:
     """The pose tail of one forward_async slot: the buffers the slot owns - per (B, cap, iterations): ws, pose, result, mask, K; the rig
     set and the covariance sets, each made when a submission first asks for it - and the launches that fill them."""
@@ -453,7 +461,7 @@ class PoseTail:
         if "coarse_pts_all" not in outs[0]:
             raise _lib.CofiError("forward_async(pose_K=...): the batched pose tail reads the outputs of match_finish, which serves fine "
                                  "feature maps of at most 128 channels; this model's fine map is wider")
-        cpts, fxy, count = outs[0]["coarse_pts_all"], outs[0]["fine_xy_all"], outs[0]["count_all"][:, 0]
+        cpts, fxy, count = outs[0]["coarse_pts_all"], image_points(outs), outs[0]["count_all"][:, 0]
         B, cap, dev = cpts.shape[0], cpts.shape[1], cpts.device
         if not torch.is_tensor(K):
             K = torch.as_tensor(np.asarray(K, dtype=np.float32))

@@ -46,6 +46,10 @@ Pose uncertainty (`pose.pose_covariance_batch` / `pose_covariance_rig` behind th
 covariance=True[, sigma_px=...])`; `covariance_result(t)` -> (cov (6,6), info (6,6), stat (4,) = [ok, rows used, sigma_hat^2, min_pivot])
 float64 of the pose of the ticket's image, `rig_covariance_result(t)` -> the same of its rig (with rig_extrinsics), in the tangent space
 (omega, v) of the left-multiplied perturbation.  sigma_px: the 1-sigma pixel noise if it is known; None estimates it from the residuals.
+
+Sub-pixel matches (`ops.fine_refine`, one launch inside every stack's recorded forward): `FrameBatcher(model, subpixel=True)`;
+`sub_xy(t)` -> (2, n), column and row on the fine map, next to `fine_xy(t)`, which stays the reference's.  With `pose=True` the poses,
+and everything behind them, are fitted to the sub-pixel points (INTEGRATION.md "Sub-pixel matches").
 """
 from typing import Dict, List, Optional, Tuple
 
@@ -58,7 +62,7 @@ from .preprocess import FrameStack
 class FrameBatcher:
     def __init__(self, model: CoFiI2P, batch: int = 16, streams: int = 4, ring: Optional[int] = None, slot_base: int = 200,
                  pose: bool = False, pose_iterations: int = 10000, eval_table=None, cameras: int = 1, rig_extrinsics=None,
-                 fuse: bool = False, covariance: bool = False, sigma_px: Optional[float] = None):
+                 fuse: bool = False, covariance: bool = False, sigma_px: Optional[float] = None, subpixel: bool = False):
         if batch < 1:
             raise ValueError("batch must be >= 1")
         if covariance and not pose:
@@ -69,6 +73,7 @@ class FrameBatcher:
             raise ValueError("FrameBatcher(sigma_px=...): a finite number > 0, or None to estimate the pixel variance")
         self.covariance = bool(covariance)
         self._pose_cov = {} if not covariance else {"pose_cov": True if sigma_px is None else float(sigma_px)}
+        self.subpixel = bool(subpixel)
         if fuse and not pose:
             raise ValueError("FrameBatcher(fuse=True): the fusion reads the poses - pass pose=True")
         if cameras < 1 or batch % cameras:
@@ -91,6 +96,7 @@ class FrameBatcher:
         self._K: List[Optional[torch.Tensor]] = [None] * self.ring   # (B,3,3) device buffer of each stack: the frames' camera matrices
         self._poses: List[Optional[Dict]] = [None] * self.ring       # handle["pose"] of the stack's finished submission
         self._fine: List[Optional[list]] = [None] * self.ring        # per-frame fine matches (2, n) of that submission
+        self._sub: List[Optional[list]] = [None] * self.ring         # per-frame sub-pixel matches (2, cap) of it (subpixel=True)
         self._counts: List[Optional[List[int]]] = [None] * self.ring  # matches per frame of that submission
         if eval_table is not None and not self.pose:
             raise ValueError("FrameBatcher(eval_table=...): the evaluation monitors read the poses - pass pose=True")
@@ -136,6 +142,7 @@ class FrameBatcher:
             self._poses[j] = h.get("pose")
             self._rig_poses[j] = h.get("rig_pose")
             self._fine[j] = h["fine_xy"]
+            self._sub[j] = [o.get("sub_xy") for o in h["out"]]
             self._counts[j] = [max(0, int(n)) for n in h["count_host"][:, 0]]
         finally:
             self._handles[j] = None
@@ -154,6 +161,8 @@ class FrameBatcher:
                                                        st.img.shape[1], st.img.device)
             rig["fuse_into"] = self._fusion[j]
         rig.update(self._pose_cov)
+        if self.subpixel:
+            rig["subpixel"] = True
         with torch.cuda.stream(self._stream(j)):
             if self.eval_table is not None:
                 self._handles[j] = self.model.forward_async(self.slot_base + j, st.pyr, st.img, inputs_stable=True, pose_K=self._K[j],
@@ -164,7 +173,7 @@ class FrameBatcher:
                                                             pose_iterations=self.pose_iterations, **rig)
             else:
                 self._handles[j] = self.model.forward_async(self.slot_base + j, st.pyr, st.img, inputs_stable=True, **rig)
-        self._results[j] = self._poses[j] = self._fine[j] = self._counts[j] = self._rig_poses[j] = None
+        self._results[j] = self._poses[j] = self._fine[j] = self._sub[j] = self._counts[j] = self._rig_poses[j] = None
         self._nsub += 1
 
     # ------------------------------------------------------------------ API
@@ -357,6 +366,15 @@ class FrameBatcher:
         """-> the fine matches (2, n) of the ticket's frame (eval_all.py:99-105; `handle["fine_xy"][f]` of the stack's submission)"""
         self.result(ticket)   # collects the submission; raises for a stale ticket or a frame without matches
         return self._fine[ticket[0]][ticket[2]]
+
+    def sub_xy(self, ticket: Tuple[int, int, int]) -> torch.Tensor:
+        """-> the sub-pixel matches (2, n) of the ticket's frame: column and row on the fine map (`handle["out"][f]["sub_xy"][:, :n]` of
+        the stack's submission; ops.fine_refine).  Same lifetime as `result(ticket)`."""
+        if not self.subpixel:
+            raise RuntimeError("FrameBatcher: built without subpixel=True")
+        self.result(ticket)   # collects the submission; raises for a stale ticket or a frame without matches
+        j, _, f = ticket
+        return self._sub[j][f][:, :self._counts[j][f]]
 
     def pose_result(self, ticket: Tuple[int, int, int]):
         """-> (result (3,) int32 [success, inliers, winning hypothesis], R (3,3), t (3,), inliers (n,) uint8) of the ticket's frame: device

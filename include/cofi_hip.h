@@ -555,6 +555,9 @@ int cofi_upsample2x_cat_nhwc(const float *low, int ldl, int C1, int h, int w, co
  * cofi_fine_match: cosine similarity of the 16 patch pixels against the point descriptor, argmax
  *   (first index on ties), fine_xy = 4*xy - 2 + (idx / 4, idx % 4)  [sic: x gets idx/4]
  *   (eval_all.py:99-105).  fine_xy (2, cap) with leading dimension `cap`.
+ * cofi_fine_refine (no counterpart in the reference; declared behind cofi_match_finish, whose outputs it reads): the matched cell
+ *   decoded geometrically - column idx % 4, row idx / 4 - plus a parabolic sub-pixel offset per axis from the similarities of its
+ *   neighbours on the map.
  */
 int cofi_row_argmin_1m(const float *sim, int lds, int N, int P, int32_t *pix, cofi_stream_t stream);
 int cofi_select_matches(const float *score, const int32_t *pix, int N, int W8, int H8, int x_max, int y_max, const float *thr_host,
@@ -589,6 +592,24 @@ int cofi_match_finish_rig(const float *pts4, const float *pts1, int N1, const in
                           const float *fmap, int ldf, int C, int H2, int W2, const float *coarse_xy, int ldxy, float center_scale,
                           const float *fine_pc_all, int ldfpc, float *coarse_pts, float *patches, float *fine_pc, int ldo,
                           float *fine_xy, int32_t *best, int N4, int frames, int cameras, cofi_stream_t stream);
+/* Sub-pixel refinement of the fine matches, behind cofi_match_finish.  Operands as that entry leaves them, in `frames`
+ * equal blocks: fmap frames x H2*W2 rows of ldf floats, coarse_xy (frames, 2, ldxy) with ldxy >= cap, fine_pc (frames, cap, ldp) - the
+ * per-match descriptor rows -, best (frames, cap), count_dev (frames, 2); outputs sub_xy (frames, 2, cap), peak (frames, cap).  Any
+ * C >= 1.  Per match i < min(count_dev[2 f], cap), in fp32:
+ *   px = floor(center_scale * x - 2) + best % 4, py = floor(center_scale * y - 2) + best / 4: the matched cell's column and row on the
+ *     map.  This is the GEOMETRIC decode of best; fine_xy (cofi_fine_match) keeps the reference caller's transposed one.
+ *   s(dx, dy) = cosine of map pixel (px + dx, py + dy) with fine_pc[i], each norm clamped at 1e-8; the channel sum runs in the same
+ *     order for all five pixels, so equal vectors give bit-equal similarities.
+ *   delta_x = 0 if px - 1 < 0 or px + 1 >= W2; else with den = (s(-1,0) - 2 s(0,0)) + s(1,0): den < 0 -> clamp(0.5 (s(-1,0) - s(1,0))
+ *     / den, -0.5, 0.5), otherwise 0.5 sign(s(1,0) - s(-1,0)) (0 for equal neighbours and for NaN).  delta_y: the same with rows.
+ *   sub_xy[0, i] = px + delta_x, sub_xy[1, i] = py + delta_y, peak[i] = s(0,0) (0 where that is not finite).
+ *   Matched cell outside the map (a zero-padded patch cell won): both offsets 0 and peak 0.
+ * With finite coarse_xy the outputs are finite whatever the map holds.  Rows i >= count_dev[2 f] are NOT written.  Frame f of a stacked
+ * call is bit-identical to a single-frame call on its slice.  16-byte loads where fmap and fine_pc are 16-byte aligned and ldf and ldp
+ * are multiples of 4; the results do not depend on it. */
+int cofi_fine_refine(const float *fmap, int ldf, int C, int H2, int W2, const float *coarse_xy, int ldxy, float center_scale,
+                     const float *fine_pc, int ldp, const int32_t *best, const int32_t *count_dev, int cap, float *sub_xy, float *peak,
+                     int frames, cofi_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Row f3, first part: the training losses of model/loss.py with their gradients w.r.t. the network outputs
