@@ -23,6 +23,8 @@
 //              the same digit find each other with 8 ballots, take consecutive slots after the digit's running offset (an LDS counter
 //              private to the wave) - stable by construction, no atomics.
 // These are latency / HBM-bound integer and streaming kernels on ~120 000 points: no MFMA anywhere.
+#include <utility>
+
 #include "common.h"
 
 namespace {
@@ -40,67 +42,121 @@ struct VoxHeader {
     int overflow;    // a voxel index did not fit KEY_BITS
 };
 
-// bounding box minimum + intensity maximum of one RED_T-row chunk -> part[block] = {min x, min y, min z, max intensity}
-__global__ __launch_bounds__(RED_T) void vox_bounds_kernel(const float *pts, int ldp, const float *inten, int ldi, int N, float *part) {
-    __shared__ float red[4][RED_T / 64];
+// The min counterpart of common.h's wave_max, and the double forms that the float64 front end reduces with.  The using-declaration keeps
+// common.h's float wave_max visible beside the double overload declared in this namespace.
+using ::wave_max;
+__device__ __forceinline__ float vmin(float a, float b) { return fminf(a, b); }
+__device__ __forceinline__ double vmin(double a, double b) { return fmin(a, b); }
+__device__ __forceinline__ float vmax(float a, float b) { return fmaxf(a, b); }
+__device__ __forceinline__ double vmax(double a, double b) { return fmax(a, b); }
+template <typename T> __device__ __forceinline__ T wave_min(T v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = vmin(v, __shfl_xor(v, o, 64));
+    return v;
+}
+__device__ __forceinline__ double wave_max(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
+    return v;
+}
+
+// bounding box minimum + intensity maximum of one RED_T-row chunk -> part[4 * block ..] = {min x, min y, min z, max intensity} in the points'
+// scalar type T (the float32 maximum widened for float64 points).  inten == nullptr: a point set without intensity, the fourth entry is -inf.
+template <typename T>
+__global__ __launch_bounds__(RED_T) void vox_bounds_kernel(const T *pts, int ldp, const float *inten, int ldi, int N, T *part) {
+    __shared__ T red[4][RED_T / 64];
     const int i = blockIdx.x * RED_T + threadIdx.x;
-    float mn[3] = {INFINITY, INFINITY, INFINITY}, mx = -INFINITY;
+    T mn[3] = {(T)INFINITY, (T)INFINITY, (T)INFINITY};
+    float mx = -INFINITY;
     if (i < N) {
 #pragma unroll
         for (int a = 0; a < 3; ++a) mn[a] = pts[(size_t)i * ldp + a];
-        mx = inten[(size_t)i * ldi];
+        if (inten) mx = inten[(size_t)i * ldi];
     }
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-#pragma unroll
-        for (int a = 0; a < 3; ++a) mn[a] = fminf(mn[a], __shfl_xor(mn[a], o, 64));
-        mx = fmaxf(mx, __shfl_xor(mx, o, 64));
-    }
+    for (int a = 0; a < 3; ++a) mn[a] = wave_min(mn[a]);
+    mx = wave_max(mx);
     const int w = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) { red[0][w] = mn[0]; red[1][w] = mn[1]; red[2][w] = mn[2]; red[3][w] = mx; }
+    if ((threadIdx.x & 63) == 0) { red[0][w] = mn[0]; red[1][w] = mn[1]; red[2][w] = mn[2]; red[3][w] = (T)mx; }
     __syncthreads();
     if (threadIdx.x < 4) {
-        float v = red[threadIdx.x][0];
-        for (int k = 1; k < RED_T / 64; ++k) v = threadIdx.x < 3 ? fminf(v, red[threadIdx.x][k]) : fmaxf(v, red[threadIdx.x][k]);
+        T v = red[threadIdx.x][0];
+        for (int k = 1; k < RED_T / 64; ++k) v = threadIdx.x < 3 ? vmin(v, red[threadIdx.x][k]) : vmax(v, red[threadIdx.x][k]);
         part[4 * blockIdx.x + threadIdx.x] = v;
     }
 }
 
-// every workgroup folds the chunk partials itself (min / max: order-free), then keys its 256 points; block 0 publishes the header
-__global__ __launch_bounds__(256) void vox_keys_kernel(const float *pts, int ldp, int N, double voxel, const float *part, int nchunk, VoxHeader *hdr,
-                                                      unsigned long long *keys, int *idx) {
-    __shared__ float red[4][4];
-    __shared__ double s_minb[3];
-    float mn[3] = {INFINITY, INFINITY, INFINITY}, mx = -INFINITY;
+// What a front end's voxel key is made of: the grid origin from the folded bounding-box minimum, the cell of a coordinate, the axis order
+// of the key, and whether block 0 publishes the origin and the intensity maximum in the header (for a mean kernel that needs them).
+//
+// open3d voxel_down_sample: voxel_min_bound = min_bound - voxel_size * 0.5 and index = floor((point - voxel_min_bound) / voxel_size), both in
+// double; x is the most significant axis.  T = float: the KITTI rows, widened per coordinate.  T = double: the nuScenes sweeps - the point is
+// NOT rounded to float32 before the subtraction (build_dataset.py:41-54 hands open3d the float64 array).
+template <typename T> struct Open3dKey {
+    typedef T point_t;
+    typedef double origin_t;
+    static constexpr bool z_major = false, publish = true;
+    double voxel;
+    __device__ double origin(T mn) const { return (double)mn - voxel * 0.5; }
+    __device__ long long cell(T p, double org) const { return (long long)floor(((double)p - org) / voxel); }
+};
+
+// grid sub-sampling of a point set (model/kpconv/ops/grid_subsample.py -> geotransformer.ext.grid_subsampling, the KPConv barycentre
+// sub-sampler): origin = floor(min * (1 / dl)) * dl, cell = floor((p - origin) / dl) per axis, all in float32 - the arithmetic of the published
+// C++ (KPConv-PyTorch cpp_wrappers/cpp_subsampling/grid_subsampling/grid_subsampling.cpp).  z is the slowest axis of its map index, so the
+// output order here is ascending (iz, iy, ix); the C++ emits its unordered_map's iteration order (unspecified).
+struct KpconvKey {
+    typedef float point_t;
+    typedef float origin_t;
+    static constexpr bool z_major = true, publish = false;
+    float dl;
+    __device__ float origin(float mn) const { return floorf(mn * (1.0f / dl)) * dl; }
+    __device__ long long cell(float p, float org) const { return (long long)floorf((p - org) / dl); }
+};
+
+__device__ __forceinline__ void load_partial(const float *p, float (&v)[4]) {
+    const f32x4 q = *reinterpret_cast<const f32x4 *>(p);
+    v[0] = q[0]; v[1] = q[1]; v[2] = q[2]; v[3] = q[3];
+}
+__device__ __forceinline__ void load_partial(const double *p, double (&v)[4]) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) v[k] = p[k];
+}
+
+// every workgroup folds the chunk partials itself (min / max: order-free), then keys its 256 points
+template <typename P>
+__global__ __launch_bounds__(256) void vox_keys_kernel(const typename P::point_t *pts, int ldp, int N, P pol, const typename P::point_t *part, int nchunk,
+                                                      VoxHeader *hdr, unsigned long long *keys, int *idx) {
+    typedef typename P::point_t T;
+    __shared__ T red[4][4];
+    __shared__ typename P::origin_t s_org[3];
+    T m[4] = {(T)INFINITY, (T)INFINITY, (T)INFINITY, -(T)INFINITY};
     for (int c = threadIdx.x; c < nchunk; c += 256) {
-        const f32x4 v = *reinterpret_cast<const f32x4 *>(part + 4 * c);
-        mn[0] = fminf(mn[0], v[0]); mn[1] = fminf(mn[1], v[1]); mn[2] = fminf(mn[2], v[2]); mx = fmaxf(mx, v[3]);
+        T v[4];
+        load_partial(part + 4 * c, v);
+        m[0] = vmin(m[0], v[0]); m[1] = vmin(m[1], v[1]); m[2] = vmin(m[2], v[2]); m[3] = vmax(m[3], v[3]);
     }
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-#pragma unroll
-        for (int a = 0; a < 3; ++a) mn[a] = fminf(mn[a], __shfl_xor(mn[a], o, 64));
-        mx = fmaxf(mx, __shfl_xor(mx, o, 64));
-    }
+    for (int a = 0; a < 3; ++a) m[a] = wave_min(m[a]);
+    m[3] = wave_max(m[3]);
     const int w = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) { red[0][w] = mn[0]; red[1][w] = mn[1]; red[2][w] = mn[2]; red[3][w] = mx; }
+    if ((threadIdx.x & 63) == 0) { red[0][w] = m[0]; red[1][w] = m[1]; red[2][w] = m[2]; red[3][w] = m[3]; }
     __syncthreads();
     if (threadIdx.x < 3) {
         const int a = threadIdx.x;
-        const float m = fminf(fminf(red[a][0], red[a][1]), fminf(red[a][2], red[a][3]));
-        s_minb[a] = (double)m - voxel * 0.5;   // open3d: voxel_min_bound = min_bound - voxel_size * 0.5, in double
-        if (blockIdx.x == 0) hdr->minb[a] = s_minb[a];
+        s_org[a] = pol.origin(vmin(vmin(red[a][0], red[a][1]), vmin(red[a][2], red[a][3])));
+        if constexpr (P::publish) if (blockIdx.x == 0) hdr->minb[a] = s_org[a];
     }
-    if (threadIdx.x == 3 && blockIdx.x == 0) hdr->imax = fmaxf(fmaxf(red[3][0], red[3][1]), fmaxf(red[3][2], red[3][3]));
+    if constexpr (P::publish)
+        if (threadIdx.x == 3 && blockIdx.x == 0) hdr->imax = (float)vmax(vmax(red[3][0], red[3][1]), vmax(red[3][2], red[3][3]));
     __syncthreads();
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= N) return;
     unsigned long long key = 0;
 #pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        // open3d: floor((point - voxel_min_bound) / voxel_size) in double
-        const double r = ((double)pts[(size_t)i * ldp + a] - s_minb[a]) / voxel;
-        long long v = (long long)floor(r);
+    for (int k = 0; k < 3; ++k) {
+        const int a = P::z_major ? 2 - k : k;
+        long long v = pol.cell(pts[(size_t)i * ldp + a], s_org[a]);
         if (v < 0 || v >= (1 << KEY_BITS)) { hdr->overflow = 1; v = v < 0 ? 0 : (1 << KEY_BITS) - 1; }
         key = (key << KEY_BITS) | (unsigned long long)v;
     }
@@ -186,28 +242,26 @@ __global__ __launch_bounds__(64 * SORT_WPB) void sort_scatter_kernel(const unsig
     }
 }
 
-// ---- segment heads of the sorted keys -> voxel ids ------------------------------------------------------------------------------
-__global__ __launch_bounds__(RED_T) void vox_head_count_kernel(const unsigned long long *keys, int N, int *chunk_heads) {
+// ---- chunked stable compaction: one flag per row, RED_T rows per workgroup.  A first launch counts every chunk's flags, a second gives
+// every flagged row its slot = flags in the chunks in front + flags in front of it in its own chunk: original order, no atomics.
+__device__ __forceinline__ void chunk_count(int flag, int *chunk_counts) {
     __shared__ int red[RED_T / 64];
-    const int i = blockIdx.x * RED_T + threadIdx.x;
-    const int h = (i < N && (i == 0 || keys[i] != keys[i - 1])) ? 1 : 0;
-    const int c = __popcll(__ballot(h));
+    const int c = __popcll(__ballot(flag));
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = c;
     __syncthreads();
     if (threadIdx.x == 0) {
         int s = 0;
         for (int k = 0; k < RED_T / 64; ++k) s += red[k];
-        chunk_heads[blockIdx.x] = s;
+        chunk_counts[blockIdx.x] = s;
     }
 }
 
-__global__ __launch_bounds__(RED_T) void vox_head_write_kernel(const unsigned long long *keys, int N, const int *chunk_heads, int nchunk, int *head_pos,
-                                                              VoxHeader *hdr, int32_t *count_dev) {
+// the slot of this thread's row (meaningful where flag is set); total = the flags of all chunks in thread 0 of the last workgroup, -1 elsewhere
+__device__ __forceinline__ int chunk_slot(int flag, const int *chunk_counts, int nchunk, int &total) {
     __shared__ int red[RED_T / 64];
     __shared__ int s_before;
-    // heads in the chunks before this one (and, for the last chunk, the total)
     int part = 0;
-    for (int c = threadIdx.x; c < (int)blockIdx.x; c += RED_T) part += chunk_heads[c];
+    for (int c = threadIdx.x; c < (int)blockIdx.x; c += RED_T) part += chunk_counts[c];
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) part += __shfl_xor(part, o, 64);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = part;
@@ -220,31 +274,59 @@ __global__ __launch_bounds__(RED_T) void vox_head_write_kernel(const unsigned lo
     __syncthreads();
     const int before = s_before;
     __syncthreads();
-    const int i = blockIdx.x * RED_T + threadIdx.x;
-    const int h = (i < N && (i == 0 || keys[i] != keys[i - 1])) ? 1 : 0;
-    const unsigned long long bal = __ballot(h);
+    const unsigned long long bal = __ballot(flag);
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     if (lane == 0) red[w] = __popcll(bal);
     __syncthreads();
     int woff = before;
     for (int k = 0; k < w; ++k) woff += red[k];
-    if (h) head_pos[woff + __popcll(bal & ((1ull << lane) - 1ull))] = i;   // voxel id -> first sorted position
+    total = -1;
     if ((int)blockIdx.x == nchunk - 1 && threadIdx.x == 0) {
-        int total = before;
+        total = before;
         for (int k = 0; k < RED_T / 64; ++k) total += red[k];
+    }
+    return woff + __popcll(bal & ((1ull << lane) - 1ull));
+}
+
+// ---- segment heads of the sorted keys -> voxel ids ------------------------------------------------------------------------------
+__device__ __forceinline__ int vox_is_head(const unsigned long long *keys, int N, int i) { return (i < N && (i == 0 || keys[i] != keys[i - 1])) ? 1 : 0; }
+
+__global__ __launch_bounds__(RED_T) void vox_head_count_kernel(const unsigned long long *keys, int N, int *chunk_heads) {
+    chunk_count(vox_is_head(keys, N, blockIdx.x * RED_T + threadIdx.x), chunk_heads);
+}
+
+__global__ __launch_bounds__(RED_T) void vox_head_write_kernel(const unsigned long long *keys, int N, const int *chunk_heads, int nchunk, int *head_pos,
+                                                              VoxHeader *hdr, int32_t *count_dev) {
+    const int i = blockIdx.x * RED_T + threadIdx.x;
+    const int h = vox_is_head(keys, N, i);
+    int total;
+    const int slot = chunk_slot(h, chunk_heads, nchunk, total);
+    if (h) head_pos[slot] = i;   // voxel id -> first sorted position
+    // count_dev[0] = voxels (may exceed the caller's cap: only the first cap rows are written), count_dev[1] = 1 if a voxel index overflowed
+    // the 13-bit key field (coordinates spread over more than 819 m at a 0.1 m voxel)
+    if (total >= 0) {
         hdr->nvox = total;
         count_dev[0] = total;
         count_dev[1] = hdr->overflow;
     }
 }
 
+// ---- one thread per voxel averages its run of the sorted order ----------------------------------------------------------------------
+// the run [b, e) of this thread's voxel v; false past the voxel count or the caller's capacity
+__device__ __forceinline__ bool voxel_run(const int *head_pos, const VoxHeader *hdr, int N, int cap, int &v, int &b, int &e) {
+    v = blockIdx.x * blockDim.x + threadIdx.x;
+    const int nv = hdr->nvox;
+    if (v >= nv || v >= cap) return false;
+    b = head_pos[v];
+    e = v + 1 < nv ? head_pos[v + 1] : N;
+    return true;
+}
+
 // out row v = [mean xyz | mean(intensity / imax) * imax | mean normal], 8 floats (last one 0)
 __global__ void vox_mean_kernel(const float *pts, int ldp, const float *inten, int ldi, const float *nrm, int ldn, const int *sorted_idx, const int *head_pos,
                                 const VoxHeader *hdr, int N, int cap, float *out) {
-    const int v = blockIdx.x * blockDim.x + threadIdx.x;
-    const int nv = hdr->nvox;
-    if (v >= nv || v >= cap) return;
-    const int b = head_pos[v], e = v + 1 < nv ? head_pos[v + 1] : N;
+    int v, b, e;
+    if (!voxel_run(head_pos, hdr, N, cap, v, b, e)) return;
     double acc[7] = {0, 0, 0, 0, 0, 0, 0};
     const float imax = hdr->imax;
     for (int s = b; s < e; ++s) {
@@ -265,47 +347,80 @@ __global__ void vox_mean_kernel(const float *pts, int ldp, const float *inten, i
     o[7] = 0.f;
 }
 
+// KPConv barycentre of every occupied cell: float32 sums in input order (grid_subsampling.cpp)
+__global__ void grid_mean_kernel(const float *pts, const int *sorted_idx, const int *head_pos, const VoxHeader *hdr, int N, int cap, float *out) {
+    int v, b, e;
+    if (!voxel_run(head_pos, hdr, N, cap, v, b, e)) return;
+    float sx = 0.f, sy = 0.f, sz = 0.f;
+    for (int s = b; s < e; ++s) {
+        const float *p = pts + (size_t)sorted_idx[s] * 3;
+        sx += p[0]; sy += p[1]; sz += p[2];
+    }
+    const float inv = (float)(1.0 / (double)(e - b));
+    out[(size_t)v * 3] = sx * inv;
+    out[(size_t)v * 3 + 1] = sy * inv;
+    out[(size_t)v * 3 + 2] = sz * inv;
+}
+
+// out row v = [float32(mean xyz) | float32(mean(float32(intensity / imax)) * (double)imax)], 4 floats.  build_dataset.py:52 multiplies the
+// float64 colour by the float32 maximum in double and :227 casts afterwards - not the float32 product of vox_mean_kernel.
+__global__ void vox_mean_f64_kernel(const double *pts, const float *inten, const int *sorted_idx, const int *head_pos, const VoxHeader *hdr, int N,
+                                    int cap, float *out) {
+    int v, b, e;
+    if (!voxel_run(head_pos, hdr, N, cap, v, b, e)) return;
+    double acc[4] = {0, 0, 0, 0};
+    const float imax = hdr->imax;
+    for (int s = b; s < e; ++s) {
+        const int i = sorted_idx[s];
+#pragma unroll
+        for (int a = 0; a < 3; ++a) acc[a] += pts[(size_t)i * 3 + a];
+        acc[3] += (double)(inten[i] / imax);
+    }
+    const double inv = 1.0 / (double)(e - b);
+    f32x4 o;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) o[a] = (float)(acc[a] * inv);
+    o[3] = (float)((acc[3] * inv) * (double)imax);
+    *reinterpret_cast<f32x4 *>(out + (size_t)v * 4) = o;
+}
+
+// y = R x (+ t) with the float32 4x4 P = [R t; 0 1].  The reference multiplies in float32 (np.dot of the float32 4x4 P with float32 arrays
+// promotes nothing: float32 BLAS) - restated as sequential float32 multiply-adds from 0 in the order k = 0, 1, 2, then the translation
+// (cofii2p_amd/dataside.py documents the same order for the oracle).
+template <bool TRANSLATE> __device__ __forceinline__ void rigid_f32(const float *P44, const float (&x)[3], float (&y)[3]) {
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        float s = 0.f;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) s = s + P44[4 * a + k] * x[k];
+        y[a] = TRANSLATE ? s + P44[4 * a + 3] : s;
+    }
+}
+
 // raw scan, channel-major (7, N) = [x y z | intensity | normal] as stored on disk  ->  rows (N, 8) = [T p | intensity | R n | 0] with the
-// calibration transform T = P_cam * Tr (kitti.py:273-277).  float32 multiply-adds in the order k = 0, 1, 2.
+// calibration transform T = P_cam * Tr (kitti.py:273-277).
 __global__ void pack_transform_kernel(const float *data, int N, const float *P44, float *rows) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= N) return;
+    const float x[3] = {data[i], data[(size_t)N + i], data[(size_t)2 * N + i]};
+    const float n[3] = {data[(size_t)4 * N + i], data[(size_t)5 * N + i], data[(size_t)6 * N + i]};
     float p[3], nn[3];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        float sp = 0.f, sn = 0.f;
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            sp = sp + P44[4 * a + k] * data[(size_t)k * N + i];
-            sn = sn + P44[4 * a + k] * data[(size_t)(4 + k) * N + i];
-        }
-        p[a] = sp + P44[4 * a + 3];
-        nn[a] = sn;
-    }
+    rigid_f32<true>(P44, x, p);
+    rigid_f32<false>(P44, n, nn);
     f32x4 lo = {p[0], p[1], p[2], data[(size_t)3 * N + i]}, hi = {nn[0], nn[1], nn[2], 0.f};
     *reinterpret_cast<f32x4 *>(rows + (size_t)i * 8) = lo;
     *reinterpret_cast<f32x4 *>(rows + (size_t)i * 8 + 4) = hi;
 }
 
 // rows choice[i] of the (nvox, 8) table -> points (n,3) = R p + t, feats (n,4) = [intensity | R n]     (kitti.py:284-288, 293)
-// The reference multiplies in float64 (np.dot of the float32 4x4 P with float32 arrays promotes nothing: float32 BLAS) - restated as
-// sequential float32 multiply-adds in the order k = 0, 1, 2 (cofii2p_amd/dataside.py documents the same order for the oracle).
 __global__ void gather_transform_kernel(const float *vox, const int32_t *choice, int n, const float *P44, float *points, float *feats, int feats_are_points) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const float *r = vox + (size_t)choice[i] * 8;
+    const float x[3] = {r[0], r[1], r[2]}, nr[3] = {r[4], r[5], r[6]};
     float p[3], nn[3];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        float sp = 0.f, sn = 0.f;
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            sp = sp + P44[4 * a + k] * r[k];
-            sn = sn + P44[4 * a + k] * r[4 + k];
-        }
-        p[a] = sp + P44[4 * a + 3];
-        nn[a] = sn;
-    }
+    rigid_f32<true>(P44, x, p);
+    rigid_f32<false>(P44, nr, nn);
     points[3 * i] = p[0]; points[3 * i + 1] = p[1]; points[3 * i + 2] = p[2];
     // KITTI: [intensity | R n] (kitti.py:293); nuScenes has no normals: [intensity | transformed point] (nuscenes.py:204)
     feats[4 * i] = r[3];
@@ -318,12 +433,8 @@ __global__ void gather_transform_kernel(const float *vox, const int32_t *choice,
 // in int32, vertical pass as the uchar specialisation of VResizeLinear writes it - each term TRUNCATED on its own,
 //     ((b0 * (S0 >> 4)) >> 16) + ((b1 * (S1 >> 4)) >> 16) + 2) >> 2
 // (not the single rounding shift by 22 of the generic FixedPtCast: the two differ by one LSB whenever the low bits of the two terms
-// carry, e.g. KITTI's 1241 x 376 -> 620 x 188) - then the crop [cy, cy + H) x [cx, cx + W), / 255 and HWC -> CHW (kitti.py:306-322, 375).  One thread per output value.
-__global__ void resize_crop_kernel(const uint8_t *src, int sh, int sw, int dh, int dw, int cy, int cx, int H, int W, float *out) {
-    const int e = blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= 3 * H * W) return;
-    const int c = e / (H * W), y = (e / W) % H, x = e % W;
-    const int dy = y + cy, dx = x + cx;
+// carry, e.g. KITTI's 1241 x 376 -> 620 x 188).  Returns channel c of destination pixel (dy, dx), clamped to [0, 255].
+__device__ __forceinline__ int cv2_resize_linear_u8(const uint8_t *src, int sh, int sw, int dh, int dw, int c, int dy, int dx) {
     const float scale_x = (float)((double)sw / dw), scale_y = (float)((double)sh / dh);   // OpenCV: double ratio used as float per coordinate
     auto coef = [](int d, float scale, int ssize, int &s0, int &a0, int &a1) {
         float f = (float)((d + 0.5) * (double)scale - 0.5);
@@ -344,64 +455,15 @@ __global__ void resize_crop_kernel(const uint8_t *src, int sh, int sw, int dh, i
     const int r0 = px(sy, sx) * ax0 + px(sy, sx1) * ax1;     // horizontal pass, scale 2^11
     const int r1 = px(sy1, sx) * ax0 + px(sy1, sx1) * ax1;
     const int v = (((ay0 * (r0 >> 4)) >> 16) + ((ay1 * (r1 >> 4)) >> 16) + 2) >> 2;    // vertical pass, VResizeLinear<uchar, int, short, ...>
-    out[e] = (float)min(max(v, 0), 255) / 255.f;
+    return min(max(v, 0), 255);
 }
 
-
-// ---- grid sub-sampling of a point set (model/kpconv/ops/grid_subsample.py -> geotransformer.ext.grid_subsampling, the KPConv
-// barycentre sub-sampler): origin = floor(min * (1 / dl)) * dl, cell = floor((p - origin) / dl) per axis, output = barycentre of every
-// occupied cell, all in float32 with sums in input order - the arithmetic of the published C++ (KPConv-PyTorch
-// cpp_wrappers/cpp_subsampling/grid_subsampling/grid_subsampling.cpp).  Output order here: ascending (iz, iy, ix) = ascending
-// map index of that code; the C++ emits its unordered_map's iteration order (unspecified).  Same sort / head-scan kernels as above.
-__global__ __launch_bounds__(256) void grid_keys_kernel(const float *pts, int N, float dl, const float *part, int nchunk, VoxHeader *hdr,
-                                                       unsigned long long *keys, int *idx) {
-    __shared__ float red[3][4];
-    __shared__ float s_org[3];
-    float mn[3] = {INFINITY, INFINITY, INFINITY};
-    for (int c = threadIdx.x; c < nchunk; c += 256) {
-        const f32x4 v = *reinterpret_cast<const f32x4 *>(part + 4 * c);
-        mn[0] = fminf(mn[0], v[0]); mn[1] = fminf(mn[1], v[1]); mn[2] = fminf(mn[2], v[2]);
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1)
-#pragma unroll
-        for (int a = 0; a < 3; ++a) mn[a] = fminf(mn[a], __shfl_xor(mn[a], o, 64));
-    const int w = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) { red[0][w] = mn[0]; red[1][w] = mn[1]; red[2][w] = mn[2]; }
-    __syncthreads();
-    if (threadIdx.x < 3) {
-        const int a = threadIdx.x;
-        const float m = fminf(fminf(red[a][0], red[a][1]), fminf(red[a][2], red[a][3]));
-        s_org[a] = floorf(m * (1.0f / dl)) * dl;
-    }
-    __syncthreads();
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= N) return;
-    unsigned long long key = 0;
-#pragma unroll
-    for (int a = 2; a >= 0; --a) {   // z is the slowest axis of the map index
-        long long v = (long long)floorf((pts[(size_t)i * 3 + a] - s_org[a]) / dl);
-        if (v < 0 || v >= (1 << KEY_BITS)) { hdr->overflow = 1; v = v < 0 ? 0 : (1 << KEY_BITS) - 1; }
-        key = (key << KEY_BITS) | (unsigned long long)v;
-    }
-    keys[i] = key;
-    idx[i] = i;
-}
-
-__global__ void grid_mean_kernel(const float *pts, const int *sorted_idx, const int *head_pos, const VoxHeader *hdr, int N, int cap, float *out) {
-    const int v = blockIdx.x * blockDim.x + threadIdx.x;
-    const int nv = hdr->nvox;
-    if (v >= nv || v >= cap) return;
-    const int b = head_pos[v], e = v + 1 < nv ? head_pos[v + 1] : N;
-    float sx = 0.f, sy = 0.f, sz = 0.f;
-    for (int s = b; s < e; ++s) {
-        const float *p = pts + (size_t)sorted_idx[s] * 3;
-        sx += p[0]; sy += p[1]; sz += p[2];
-    }
-    const float inv = (float)(1.0 / (double)(e - b));
-    out[(size_t)v * 3] = sx * inv;
-    out[(size_t)v * 3 + 1] = sy * inv;
-    out[(size_t)v * 3 + 2] = sz * inv;
+// the resized picture's crop [cy, cy + H) x [cx, cx + W), / 255 and HWC -> CHW (kitti.py:306-322, 375).  One thread per output value.
+__global__ void resize_crop_kernel(const uint8_t *src, int sh, int sw, int dh, int dw, int cy, int cx, int H, int W, float *out) {
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= 3 * H * W) return;
+    const int c = e / (H * W), y = (e / W) % H, x = e % W;
+    out[e] = (float)cv2_resize_linear_u8(src, sh, sw, dh, dw, c, y + cy, x + cx) / 255.f;
 }
 
 // out[m][j] = idx[m][j] + offset if dist[m][j] < r2 (and the slot is a real neighbour) else fill; max_count[0] = max over rows of the
@@ -500,41 +562,16 @@ __device__ __forceinline__ bool sweep_on_ego(float x, float y) { return (x < 0.8
 
 // kept rows of one RED_T-row chunk of the concatenated sweeps
 __global__ __launch_bounds__(RED_T) void sweep_keep_count_kernel(const float *rows, int ld, int total, int *chunk_keep) {
-    __shared__ int red[RED_T / 64];
     const int i = blockIdx.x * RED_T + threadIdx.x;
-    const int k = (i < total && !sweep_on_ego(rows[(size_t)i * ld], rows[(size_t)i * ld + 1])) ? 1 : 0;
-    const int c = __popcll(__ballot(k));
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int s = 0;
-        for (int w = 0; w < RED_T / 64; ++w) s += red[w];
-        chunk_keep[blockIdx.x] = s;
-    }
+    chunk_count((i < total && !sweep_on_ego(rows[(size_t)i * ld], rows[(size_t)i * ld + 1])) ? 1 : 0, chunk_keep);
 }
 
-// :127-185: kept rows in sweep order, then original order (stable compaction: chunk offsets + ballot ranks).  Sweep 0 is widened
+// :127-185: kept rows in sweep order, then original order (the stable compaction above).  Sweep 0 is widened
 // untransformed, sweep j > 0 goes through T_j in double: s = T[a][0] * x; s = s + T[a][1] * y; s = s + T[a][2] * z; s = s + T[a][3].
 __global__ __launch_bounds__(RED_T) void sweep_write_kernel(const float *rows, int ld, const int32_t *offsets, int S, int total, const double *T,
                                                            const int *chunk_keep, int nchunk, double *pts, float *inten, int32_t *count_dev) {
-    __shared__ int red[RED_T / 64];
-    __shared__ int s_before;
     __shared__ int s_off[64];
-    if ((int)threadIdx.x < S) s_off[threadIdx.x] = offsets[threadIdx.x];
-    int part = 0;
-    for (int c = threadIdx.x; c < (int)blockIdx.x; c += RED_T) part += chunk_keep[c];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) part += __shfl_xor(part, o, 64);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = part;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int s = 0;
-        for (int k = 0; k < RED_T / 64; ++k) s += red[k];
-        s_before = s;
-    }
-    __syncthreads();
-    const int before = s_before;
-    __syncthreads();
+    if ((int)threadIdx.x < S) s_off[threadIdx.x] = offsets[threadIdx.x];   // read after the barriers of chunk_slot
     const int i = blockIdx.x * RED_T + threadIdx.x;
     float x = 0.f, y = 0.f, z = 0.f, r = 0.f;
     int keep = 0;
@@ -543,19 +580,14 @@ __global__ __launch_bounds__(RED_T) void sweep_write_kernel(const float *rows, i
         x = p[0]; y = p[1]; z = p[2]; r = p[3];
         keep = !sweep_on_ego(x, y);
     }
-    const unsigned long long bal = __ballot(keep);
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    if (lane == 0) red[w] = __popcll(bal);
-    __syncthreads();
-    int woff = before;
-    for (int k = 0; k < w; ++k) woff += red[k];
+    int kept;
+    const size_t o = (size_t)chunk_slot(keep, chunk_keep, nchunk, kept);
     if (keep) {
         int lo = 0, hi = S - 1;   // the sweep of row i: the last j with offsets[j] <= i (empty sweeps share an offset with their successor)
         while (lo < hi) {
             const int mid = (lo + hi + 1) >> 1;
             if (s_off[mid] <= i) lo = mid; else hi = mid - 1;
         }
-        const size_t o = (size_t)(woff + __popcll(bal & ((1ull << lane) - 1ull)));
         const double dx = (double)x, dy = (double)y, dz = (double)z;
         if (lo == 0) {
             pts[3 * o] = dx; pts[3 * o + 1] = dy; pts[3 * o + 2] = dz;
@@ -572,105 +604,7 @@ __global__ __launch_bounds__(RED_T) void sweep_write_kernel(const float *rows, i
         }
         inten[o] = r;
     }
-    if ((int)blockIdx.x == nchunk - 1 && threadIdx.x == 0) {
-        int t = before;
-        for (int k = 0; k < RED_T / 64; ++k) t += red[k];
-        count_dev[0] = t;
-    }
-}
-
-// float64 points: bounding box minimum (double) + intensity maximum of one RED_T-row chunk -> part[4 * block ..] = {min x, min y, min z, max
-// intensity widened}
-__global__ __launch_bounds__(RED_T) void vox_bounds_f64_kernel(const double *pts, const float *inten, int N, double *part) {
-    __shared__ double red[4][RED_T / 64];
-    const int i = blockIdx.x * RED_T + threadIdx.x;
-    double mn[3] = {(double)INFINITY, (double)INFINITY, (double)INFINITY};
-    float mx = -INFINITY;
-    if (i < N) {
-#pragma unroll
-        for (int a = 0; a < 3; ++a) mn[a] = pts[(size_t)i * 3 + a];
-        mx = inten[i];
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-#pragma unroll
-        for (int a = 0; a < 3; ++a) mn[a] = fmin(mn[a], __shfl_xor(mn[a], o, 64));
-        mx = fmaxf(mx, __shfl_xor(mx, o, 64));
-    }
-    const int w = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) { red[0][w] = mn[0]; red[1][w] = mn[1]; red[2][w] = mn[2]; red[3][w] = (double)mx; }
-    __syncthreads();
-    if (threadIdx.x < 4) {
-        double v = red[threadIdx.x][0];
-        for (int k = 1; k < RED_T / 64; ++k) v = threadIdx.x < 3 ? fmin(v, red[threadIdx.x][k]) : fmax(v, red[threadIdx.x][k]);
-        part[4 * blockIdx.x + threadIdx.x] = v;
-    }
-}
-
-// vox_keys_kernel on float64 points: the point is NOT rounded to float32 before floor((p - minb) / voxel) (build_dataset.py:41-54 hands
-// open3d the float64 array)
-__global__ __launch_bounds__(256) void vox_keys_f64_kernel(const double *pts, int N, double voxel, const double *part, int nchunk, VoxHeader *hdr,
-                                                          unsigned long long *keys, int *idx) {
-    __shared__ double red[4][4];
-    __shared__ double s_minb[3];
-    double mn[3] = {(double)INFINITY, (double)INFINITY, (double)INFINITY}, mx = -(double)INFINITY;
-    for (int c = threadIdx.x; c < nchunk; c += 256) {
-        const double *v = part + 4 * c;
-        mn[0] = fmin(mn[0], v[0]); mn[1] = fmin(mn[1], v[1]); mn[2] = fmin(mn[2], v[2]); mx = fmax(mx, v[3]);
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-#pragma unroll
-        for (int a = 0; a < 3; ++a) mn[a] = fmin(mn[a], __shfl_xor(mn[a], o, 64));
-        mx = fmax(mx, __shfl_xor(mx, o, 64));
-    }
-    const int w = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) { red[0][w] = mn[0]; red[1][w] = mn[1]; red[2][w] = mn[2]; red[3][w] = mx; }
-    __syncthreads();
-    if (threadIdx.x < 3) {
-        const int a = threadIdx.x;
-        const double m = fmin(fmin(red[a][0], red[a][1]), fmin(red[a][2], red[a][3]));
-        s_minb[a] = m - voxel * 0.5;
-        if (blockIdx.x == 0) hdr->minb[a] = s_minb[a];
-    }
-    if (threadIdx.x == 3 && blockIdx.x == 0) hdr->imax = (float)fmax(fmax(red[3][0], red[3][1]), fmax(red[3][2], red[3][3]));
-    __syncthreads();
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= N) return;
-    unsigned long long key = 0;
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        const double r = (pts[(size_t)i * 3 + a] - s_minb[a]) / voxel;
-        long long v = (long long)floor(r);
-        if (v < 0 || v >= (1 << KEY_BITS)) { hdr->overflow = 1; v = v < 0 ? 0 : (1 << KEY_BITS) - 1; }
-        key = (key << KEY_BITS) | (unsigned long long)v;
-    }
-    keys[i] = key;
-    idx[i] = i;
-}
-
-// out row v = [float32(mean xyz) | float32(mean(float32(intensity / imax)) * (double)imax)], 4 floats.  build_dataset.py:52 multiplies the
-// float64 colour by the float32 maximum in double and :227 casts afterwards - not the float32 product of vox_mean_kernel.
-__global__ void vox_mean_f64_kernel(const double *pts, const float *inten, const int *sorted_idx, const int *head_pos, const VoxHeader *hdr, int N,
-                                    int cap, float *out) {
-    const int v = blockIdx.x * blockDim.x + threadIdx.x;
-    const int nv = hdr->nvox;
-    if (v >= nv || v >= cap) return;
-    const int b = head_pos[v], e = v + 1 < nv ? head_pos[v + 1] : N;
-    double acc[4] = {0, 0, 0, 0};
-    const float imax = hdr->imax;
-    for (int s = b; s < e; ++s) {
-        const int i = sorted_idx[s];
-#pragma unroll
-        for (int a = 0; a < 3; ++a) acc[a] += pts[(size_t)i * 3 + a];
-        acc[3] += (double)(inten[i] / imax);
-    }
-    const double inv = 1.0 / (double)(e - b);
-    f32x4 o;
-#pragma unroll
-    for (int a = 0; a < 3; ++a) o[a] = (float)(acc[a] * inv);
-    o[3] = (float)((acc[3] * inv) * (double)imax);
-    *reinterpret_cast<f32x4 *>(out + (size_t)v * 4) = o;
+    if (kept >= 0) count_dev[0] = kept;
 }
 
 // :265-280: c = R p + t (float64 P_cam_pc, float32 point widened), uvz = K c (float32 K widened), each a chain of separate double products
@@ -709,45 +643,82 @@ __global__ __launch_bounds__(256) void sweeps_camera_kernel(const float *rows4, 
     if ((threadIdx.x & 63) == 0 && cnt) atomicAdd(inside, cnt);   // integer: order-free
 }
 
-// build_dataset.py:252-260: rows [top, sh) of the uint8 HWC image through cv2.resize(INTER_LINEAR), the arithmetic of resize_crop_kernel,
-// the clamped integer stored as uint8 HWC.  One thread per output value.
+// build_dataset.py:252-260: rows [top, sh) of the uint8 HWC image through cv2.resize(INTER_LINEAR), the clamped integer stored as uint8 HWC.
+// One thread per output value.
 __global__ void resize_u8_kernel(const uint8_t *src, int sh, int sw, int dh, int dw, uint8_t *out) {
     const int e = blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= 3 * dh * dw) return;
     const int c = e % 3, dx = (e / 3) % dw, dy = e / (3 * dw);
-    const float scale_x = (float)((double)sw / dw), scale_y = (float)((double)sh / dh);
-    auto coef = [](int d, float scale, int ssize, int &s0, int &a0, int &a1) {
-        float f = (float)((d + 0.5) * (double)scale - 0.5);
-        int s = (int)floorf(f);
-        f -= s;
-        if (s < 0) { f = 0.f; s = 0; }
-        if (s >= ssize - 1) { f = 0.f; s = ssize - 1; }
-        s0 = s;
-        a0 = (int)rintf((1.f - f) * 2048.f);
-        a1 = (int)rintf(f * 2048.f);
-    };
-    int sx, ax0, ax1, sy, ay0, ay1;
-    coef(dx, scale_x, sw, sx, ax0, ax1);
-    coef(dy, scale_y, sh, sy, ay0, ay1);
-    const int sx1 = min(sx + 1, sw - 1), sy1 = min(sy + 1, sh - 1);
-    auto px = [&](int yy, int xx) { return (int)src[((size_t)yy * sw + xx) * 3 + c]; };
-    const int r0 = px(sy, sx) * ax0 + px(sy, sx1) * ax1;
-    const int r1 = px(sy1, sx) * ax0 + px(sy1, sx1) * ax1;
-    const int v = (((ay0 * (r0 >> 4)) >> 16) + ((ay1 * (r1 >> 4)) >> 16) + 2) >> 2;
-    out[e] = (uint8_t)min(max(v, 0), 255);
+    out[e] = (uint8_t)cv2_resize_linear_u8(src, sh, sw, dh, dw, c, dy, dx);
 }
 
 }  // namespace
 
 static inline size_t vox_align(size_t v) { return (v + 255) & ~(size_t)255; }
 
-extern "C" size_t cofi_voxel_downsample_workspace(int N) {
-    if (N <= 0) return 0;
-    // header | chunk partials (bounds: 4 floats, heads: 1 int per 1024 rows) | histogram table + digit totals | keys A, B | idx A, B | heads
-    const size_t nchunk = (size_t)cofi_cdiv(N, RED_T);
-    return 256 + vox_align(nchunk * 16) + vox_align(nchunk * 4) + vox_align((size_t)(256 * SORT_TILES + 256) * 4) + 2 * vox_align((size_t)N * 8) +
-           3 * vox_align((size_t)N * 4);
+// The workspace of one voxel grid over N points:
+//   header | chunk partials (bounds: partial_bytes = 4 scalars of the points' type, heads: 1 int per RED_T rows) | histogram table + digit
+//   totals | keys A, B | idx A, B | heads
+// The only statement of the layout: a *_workspace size is `bytes` of the carve-up of address 0.
+struct VoxWorkspace {
+    VoxHeader *hdr;
+    void *bounds;
+    int *chunk_heads, *hist, *tot;
+    unsigned long long *keys[2];
+    int *idx[2];
+    int *heads;
+    size_t bytes;
+
+    VoxWorkspace(void *ws, int N, size_t partial_bytes) {
+        const size_t nchunk = (size_t)cofi_cdiv(N, RED_T);
+        uintptr_t w = (uintptr_t)ws;
+        auto take = [&w](size_t n) { void *p = (void *)w; w += vox_align(n); return p; };
+        hdr = (VoxHeader *)take(256);
+        bounds = take(nchunk * partial_bytes);
+        chunk_heads = (int *)take(nchunk * 4);
+        hist = (int *)take((size_t)(256 * SORT_TILES + 256) * 4);
+        tot = hist + 256 * SORT_TILES;
+        for (int k = 0; k < 2; ++k) keys[k] = (unsigned long long *)take((size_t)N * 8);
+        for (int k = 0; k < 2; ++k) idx[k] = (int *)take((size_t)N * 4);
+        heads = (int *)take((size_t)N * 4);
+        bytes = w - (uintptr_t)ws;
+    }
+};
+
+// the stable radix sort of the (key, index) pairs in keys[0] / idx[0]: the buffers change roles after every pass, [0] holds the result
+static void sort_pairs(VoxWorkspace &W, int N, hipStream_t s) {
+    const int tile = cofi_cdiv(N, SORT_TILES);
+    for (int pass = 0; pass < SORT_PASSES; ++pass) {
+        hipLaunchKernelGGL(sort_hist_kernel, dim3(SORT_TILES / SORT_WPB), dim3(64 * SORT_WPB), 0, s, W.keys[0], N, 8 * pass, tile, W.hist);
+        hipLaunchKernelGGL(sort_scan_kernel, dim3(64), dim3(256), 0, s, W.hist, W.tot);
+        hipLaunchKernelGGL(sort_scatter_kernel, dim3(SORT_TILES / SORT_WPB), dim3(64 * SORT_WPB), 0, s, W.keys[0], W.idx[0], W.keys[1], W.idx[1], N, 8 * pass,
+                           tile, W.hist, W.tot);
+        std::swap(W.keys[0], W.keys[1]);
+        std::swap(W.idx[0], W.idx[1]);
+    }
 }
+
+// One voxel grid: memset -> bounds -> keys -> sort -> head count -> head write -> mean.  The key policy P says what the front end's voxels
+// are; launch_mean(grid, block, sorted_idx, head_pos, hdr) launches its mean kernel, one thread per voxel.  inten may be null.
+template <typename P, typename LaunchMean>
+static int voxel_grid(const typename P::point_t *pts, int ldp, const float *inten, int ldi, int N, P key, int32_t *count_dev, void *ws, hipStream_t s,
+                      LaunchMean launch_mean) {
+    typedef typename P::point_t T;
+    VoxWorkspace W(ws, N, 4 * sizeof(T));
+    const int nchunk = cofi_cdiv(N, RED_T);
+    (void)hipMemsetAsync(W.hdr, 0, sizeof(VoxHeader), s);
+    hipLaunchKernelGGL(vox_bounds_kernel<T>, dim3(nchunk), dim3(RED_T), 0, s, pts, ldp, inten, ldi, N, (T *)W.bounds);
+    hipLaunchKernelGGL(vox_keys_kernel<P>, dim3(cofi_cdiv(N, 256)), dim3(256), 0, s, pts, ldp, N, key, (const T *)W.bounds, nchunk, W.hdr, W.keys[0], W.idx[0]);
+    sort_pairs(W, N, s);
+    hipLaunchKernelGGL(vox_head_count_kernel, dim3(nchunk), dim3(RED_T), 0, s, W.keys[0], N, W.chunk_heads);
+    hipLaunchKernelGGL(vox_head_write_kernel, dim3(nchunk), dim3(RED_T), 0, s, W.keys[0], N, W.chunk_heads, nchunk, W.heads, W.hdr, count_dev);
+    launch_mean(dim3(cofi_cdiv(N, 256)), dim3(256), W.idx[0], W.heads, W.hdr);
+    return cofi_launch_status();
+}
+
+extern "C" size_t cofi_voxel_downsample_workspace(int N) { return N <= 0 ? 0 : VoxWorkspace(nullptr, N, 4 * sizeof(float)).bytes; }
+
+extern "C" size_t cofi_voxel_downsample_f64_workspace(int N) { return N <= 0 ? 0 : VoxWorkspace(nullptr, N, 4 * sizeof(double)).bytes; }
 
 extern "C" int cofi_pack_transform_scan(const float *data7n, int N, const float *P44_dev, float *rows8, cofi_stream_t stream) {
     if (!data7n || !P44_dev || !rows8 || N <= 0 || ((uintptr_t)rows8 & 15)) return COFI_EINVAL;
@@ -762,35 +733,11 @@ extern "C" int cofi_voxel_downsample(const float *rows8, int N, double voxel, fl
     hipStream_t s = cofi_s(stream);
     const float *points = rows8, *intensity = rows8 + 3, *normals = rows8 + 4;
     const int ldp = 8, ldi = 8, ldn = 8;
-    const int nchunk = cofi_cdiv(N, RED_T);
-    char *w = (char *)ws;
-    VoxHeader *hdr = (VoxHeader *)w; w += 256;
-    float *bpart = (float *)w; w += vox_align((size_t)nchunk * 16);
-    int *hpart = (int *)w; w += vox_align((size_t)nchunk * 4);
-    int *hist = (int *)w, *tot = hist + 256 * SORT_TILES; w += vox_align((size_t)(256 * SORT_TILES + 256) * 4);
-    unsigned long long *kA = (unsigned long long *)w; w += vox_align((size_t)N * 8);
-    unsigned long long *kB = (unsigned long long *)w; w += vox_align((size_t)N * 8);
-    int *vA = (int *)w; w += vox_align((size_t)N * 4);
-    int *vB = (int *)w; w += vox_align((size_t)N * 4);
-    int *heads = (int *)w;
-    (void)hipMemsetAsync(hdr, 0, sizeof(VoxHeader), s);
-    hipLaunchKernelGGL(vox_bounds_kernel, dim3(nchunk), dim3(RED_T), 0, s, points, ldp, intensity, ldi, N, bpart);
-    hipLaunchKernelGGL(vox_keys_kernel, dim3(cofi_cdiv(N, 256)), dim3(256), 0, s, points, ldp, N, voxel, bpart, nchunk, hdr, kA, vA);
-    const int tile = cofi_cdiv(N, SORT_TILES);
-    for (int pass = 0; pass < SORT_PASSES; ++pass) {
-        hipLaunchKernelGGL(sort_hist_kernel, dim3(SORT_TILES / SORT_WPB), dim3(64 * SORT_WPB), 0, s, kA, N, 8 * pass, tile, hist);
-        hipLaunchKernelGGL(sort_scan_kernel, dim3(64), dim3(256), 0, s, hist, tot);
-        hipLaunchKernelGGL(sort_scatter_kernel, dim3(SORT_TILES / SORT_WPB), dim3(64 * SORT_WPB), 0, s, kA, vA, kB, vB, N, 8 * pass, tile, hist, tot);
-        unsigned long long *tk = kA; kA = kB; kB = tk;
-        int *tv = vA; vA = vB; vB = tv;
-    }
-    hipLaunchKernelGGL(vox_head_count_kernel, dim3(nchunk), dim3(RED_T), 0, s, kA, N, hpart);
-    hipLaunchKernelGGL(vox_head_write_kernel, dim3(nchunk), dim3(RED_T), 0, s, kA, N, hpart, nchunk, heads, hdr, count_dev);
-    hipLaunchKernelGGL(vox_mean_kernel, dim3(cofi_cdiv(N, 256)), dim3(256), 0, s, points, ldp, intensity, ldi, normals, ldn, vA, heads, hdr, N, cap,
-                       out_rows8);
-    // count_dev[0] = voxels (may exceed cap: only the first cap rows were written), count_dev[1] = 1 if a voxel index overflowed the
-    // 13-bit key field (coordinates spread over more than 819 m at this voxel size) - written by the last head-scan workgroup
-    return cofi_launch_status();
+    return voxel_grid(points, ldp, intensity, ldi, N, Open3dKey<float>{voxel}, count_dev, ws, s,
+                      [&](dim3 grid, dim3 block, const int *sorted_idx, const int *head_pos, const VoxHeader *hdr) {
+                          hipLaunchKernelGGL(vox_mean_kernel, grid, block, 0, s, points, ldp, intensity, ldi, normals, ldn, sorted_idx, head_pos, hdr, N, cap,
+                                             out_rows8);
+                      });
 }
 
 extern "C" int cofi_grid_subsample(const float *points, int N, float voxel, float *out_points, int cap, int32_t *count_dev, void *ws, size_t ws_bytes,
@@ -798,32 +745,10 @@ extern "C" int cofi_grid_subsample(const float *points, int N, float voxel, floa
     if (!points || !out_points || !count_dev || N <= 0 || !(voxel > 0.f) || cap <= 0) return COFI_EINVAL;
     if (!ws || ws_bytes < cofi_voxel_downsample_workspace(N) || ((uintptr_t)ws & 15)) return COFI_EWORKSPACE;
     hipStream_t s = cofi_s(stream);
-    const int nchunk = cofi_cdiv(N, RED_T);
-    char *w = (char *)ws;
-    VoxHeader *hdr = (VoxHeader *)w; w += 256;
-    float *bpart = (float *)w; w += vox_align((size_t)nchunk * 16);
-    int *hpart = (int *)w; w += vox_align((size_t)nchunk * 4);
-    int *hist = (int *)w, *tot = hist + 256 * SORT_TILES; w += vox_align((size_t)(256 * SORT_TILES + 256) * 4);
-    unsigned long long *kA = (unsigned long long *)w; w += vox_align((size_t)N * 8);
-    unsigned long long *kB = (unsigned long long *)w; w += vox_align((size_t)N * 8);
-    int *vA = (int *)w; w += vox_align((size_t)N * 4);
-    int *vB = (int *)w; w += vox_align((size_t)N * 4);
-    int *heads = (int *)w;
-    (void)hipMemsetAsync(hdr, 0, sizeof(VoxHeader), s);
-    hipLaunchKernelGGL(vox_bounds_kernel, dim3(nchunk), dim3(RED_T), 0, s, points, 3, points, 3, N, bpart);
-    hipLaunchKernelGGL(grid_keys_kernel, dim3(cofi_cdiv(N, 256)), dim3(256), 0, s, points, N, voxel, bpart, nchunk, hdr, kA, vA);
-    const int tile = cofi_cdiv(N, SORT_TILES);
-    for (int pass = 0; pass < SORT_PASSES; ++pass) {
-        hipLaunchKernelGGL(sort_hist_kernel, dim3(SORT_TILES / SORT_WPB), dim3(64 * SORT_WPB), 0, s, kA, N, 8 * pass, tile, hist);
-        hipLaunchKernelGGL(sort_scan_kernel, dim3(64), dim3(256), 0, s, hist, tot);
-        hipLaunchKernelGGL(sort_scatter_kernel, dim3(SORT_TILES / SORT_WPB), dim3(64 * SORT_WPB), 0, s, kA, vA, kB, vB, N, 8 * pass, tile, hist, tot);
-        unsigned long long *tk = kA; kA = kB; kB = tk;
-        int *tv = vA; vA = vB; vB = tv;
-    }
-    hipLaunchKernelGGL(vox_head_count_kernel, dim3(nchunk), dim3(RED_T), 0, s, kA, N, hpart);
-    hipLaunchKernelGGL(vox_head_write_kernel, dim3(nchunk), dim3(RED_T), 0, s, kA, N, hpart, nchunk, heads, hdr, count_dev);
-    hipLaunchKernelGGL(grid_mean_kernel, dim3(cofi_cdiv(N, 256)), dim3(256), 0, s, points, vA, heads, hdr, N, cap, out_points);
-    return cofi_launch_status();
+    return voxel_grid(points, 3, nullptr, 0, N, KpconvKey{voxel}, count_dev, ws, s,
+                      [&](dim3 grid, dim3 block, const int *sorted_idx, const int *head_pos, const VoxHeader *hdr) {
+                          hipLaunchKernelGGL(grid_mean_kernel, grid, block, 0, s, points, sorted_idx, head_pos, hdr, N, cap, out_points);
+                      });
 }
 
 extern "C" int cofi_radius_mask(const int32_t *idx, const float *dist, int M, int k, int S, float radius, long long offset, long long fill,
@@ -896,46 +821,16 @@ extern "C" int cofi_accumulate_sweeps(const float *rows, int ld, const int32_t *
     return cofi_launch_status();
 }
 
-extern "C" size_t cofi_voxel_downsample_f64_workspace(int N) {
-    if (N <= 0) return 0;
-    // as cofi_voxel_downsample_workspace, with 4 doubles of bounds per chunk
-    const size_t nchunk = (size_t)cofi_cdiv(N, RED_T);
-    return 256 + vox_align(nchunk * 32) + vox_align(nchunk * 4) + vox_align((size_t)(256 * SORT_TILES + 256) * 4) + 2 * vox_align((size_t)N * 8) +
-           3 * vox_align((size_t)N * 4);
-}
-
 extern "C" int cofi_voxel_downsample_f64(const double *points, const float *intensity, int N, double voxel, float *out_rows4, int cap,
                                          int32_t *count_dev, void *ws, size_t ws_bytes, cofi_stream_t stream) {
     if (!points || !intensity || !out_rows4 || !count_dev || N <= 0 || !(voxel > 0.0) || cap <= 0) return COFI_EINVAL;
     if (((uintptr_t)points & 7) || ((uintptr_t)out_rows4 & 15)) return COFI_EINVAL;
     if (!ws || ws_bytes < cofi_voxel_downsample_f64_workspace(N) || ((uintptr_t)ws & 15)) return COFI_EWORKSPACE;
     hipStream_t s = cofi_s(stream);
-    const int nchunk = cofi_cdiv(N, RED_T);
-    char *w = (char *)ws;
-    VoxHeader *hdr = (VoxHeader *)w; w += 256;
-    double *bpart = (double *)w; w += vox_align((size_t)nchunk * 32);
-    int *hpart = (int *)w; w += vox_align((size_t)nchunk * 4);
-    int *hist = (int *)w, *tot = hist + 256 * SORT_TILES; w += vox_align((size_t)(256 * SORT_TILES + 256) * 4);
-    unsigned long long *kA = (unsigned long long *)w; w += vox_align((size_t)N * 8);
-    unsigned long long *kB = (unsigned long long *)w; w += vox_align((size_t)N * 8);
-    int *vA = (int *)w; w += vox_align((size_t)N * 4);
-    int *vB = (int *)w; w += vox_align((size_t)N * 4);
-    int *heads = (int *)w;
-    (void)hipMemsetAsync(hdr, 0, sizeof(VoxHeader), s);
-    hipLaunchKernelGGL(vox_bounds_f64_kernel, dim3(nchunk), dim3(RED_T), 0, s, points, intensity, N, bpart);
-    hipLaunchKernelGGL(vox_keys_f64_kernel, dim3(cofi_cdiv(N, 256)), dim3(256), 0, s, points, N, voxel, bpart, nchunk, hdr, kA, vA);
-    const int tile = cofi_cdiv(N, SORT_TILES);
-    for (int pass = 0; pass < SORT_PASSES; ++pass) {
-        hipLaunchKernelGGL(sort_hist_kernel, dim3(SORT_TILES / SORT_WPB), dim3(64 * SORT_WPB), 0, s, kA, N, 8 * pass, tile, hist);
-        hipLaunchKernelGGL(sort_scan_kernel, dim3(64), dim3(256), 0, s, hist, tot);
-        hipLaunchKernelGGL(sort_scatter_kernel, dim3(SORT_TILES / SORT_WPB), dim3(64 * SORT_WPB), 0, s, kA, vA, kB, vB, N, 8 * pass, tile, hist, tot);
-        unsigned long long *tk = kA; kA = kB; kB = tk;
-        int *tv = vA; vA = vB; vB = tv;
-    }
-    hipLaunchKernelGGL(vox_head_count_kernel, dim3(nchunk), dim3(RED_T), 0, s, kA, N, hpart);
-    hipLaunchKernelGGL(vox_head_write_kernel, dim3(nchunk), dim3(RED_T), 0, s, kA, N, hpart, nchunk, heads, hdr, count_dev);
-    hipLaunchKernelGGL(vox_mean_f64_kernel, dim3(cofi_cdiv(N, 256)), dim3(256), 0, s, points, intensity, vA, heads, hdr, N, cap, out_rows4);
-    return cofi_launch_status();
+    return voxel_grid(points, 3, intensity, 1, N, Open3dKey<double>{voxel}, count_dev, ws, s,
+                      [&](dim3 grid, dim3 block, const int *sorted_idx, const int *head_pos, const VoxHeader *hdr) {
+                          hipLaunchKernelGGL(vox_mean_f64_kernel, grid, block, 0, s, points, intensity, sorted_idx, head_pos, hdr, N, cap, out_rows4);
+                      });
 }
 
 extern "C" int cofi_sweeps_to_camera(const float *rows4, int M, const double *P44_dev, const float *K33_dev, int H, int W, float *out_4m,

@@ -49,7 +49,7 @@ def oracle_voxel(data, P_Tr):
     return D.voxel_down_sample(pc, data[3:4], sn, 0.1), pc, sn
 
 
-@pytest.mark.parametrize("n_points", [120000, 30000, 1500, 700, 1])
+@pytest.mark.parametrize("n_points", [120000, 30000, 1500, 700, 1, 1023, 1024, 1025, 2048])   # the last four: the 1024-row chunk edge
 def test_voxel_grid_against_oracle(ds, n_points):
     from cofii2p_amd import synth
 

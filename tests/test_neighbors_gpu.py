@@ -23,7 +23,8 @@ def cloud(seed, n, extent=20.0):
     return p
 
 
-@pytest.mark.parametrize("lengths,voxel", [([5000], 0.3), ([20480, 9000, 1], 0.6), ([300, 0, 700], 2.5), ([40000], 0.15)])
+@pytest.mark.parametrize("lengths,voxel", [([5000], 0.3), ([20480, 9000, 1], 0.6), ([300, 0, 700], 2.5), ([40000], 0.15),
+                                           ([1024, 1023, 1025], 0.6)])   # the 1024-row chunk edge
 def test_grid_subsample_against_oracle(lengths, voxel):
     from model.kpconv.ops import grid_subsample   # the reference's import path
 

@@ -148,7 +148,7 @@ def test_voxel_all_points_in_one_voxel(sw):
     assert check_voxel(sw, pts, g.uniform(0, 255, 3000).astype(E)) == 1
 
 
-@pytest.mark.parametrize("n", [1500, 5000])
+@pytest.mark.parametrize("n", [1500, 5000, 1023, 1024, 1025, 2049])   # the last four: the 1024-row chunk edge
 def test_voxel_random_points(sw, n):
     g = np.random.default_rng(21)
     pts = g.uniform(-4.0, 4.0, (n, 3))
